@@ -8,9 +8,15 @@ starts; --data device|pinned puts the training data path (dataset_single_member.
 HBM gather kernel, or host gather + pinned side-stream H2D) inside the timed region.
 
   python bench.py [--gpus N --steps K --warmup W --batch B --frames F --config more_blocks]
+                   [--dump-outputs DIR] [--full]
   N>1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...); `roofline` and `top_kernels` are null in it.
+--dump-outputs DIR then writes what the last timed step produced (loss.npy, params.npy, grads.npy; float32,
+a fixed seeded sample of the flat parameter / gradient vectors when they are large) so that two builds can be
+compared output for output: the weights, the batch and the t / eps stream are seeded, the same from run to run.
+With --full the line also carries
   roofline      the DOMINANT kernel by time per step: chosen from HIP events around every launch of the
                 profiled ops in the last two warm-up steps, then timed live over the timed steps (events on the
                 stream it runs on, around its launches only, so the timed region stays uninstrumented otherwise):
@@ -18,8 +24,10 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                 PMC traffic measured at the bench batch (profiles/step_traffic.json);
   top_kernels   the five most expensive kernels by time per step (from the profiled warm-up steps), same fields;
   cpu_baseline  oracle fp32 train steps on the host cores (SURVEY.md §8(d) D5);
-  fwd_error     forward error of the HIP path vs the CPU oracle (the metric's "fwd MSE vs ref").
-The last two come from the CPU leg (`cpu_leg`), the only part of this file that touches oracle/.
+  fwd_error     forward error of the HIP path vs the CPU oracle (the metric's "fwd MSE vs ref");
+  other_configs the extra single-GPU legs (OTHER_CONFIGS), each with its own roofline / top_kernels.
+cpu_baseline and fwd_error come from the CPU leg (`cpu_leg`), the only part of this file that touches oracle/.
+--no-probe, --no-cpu-baseline, --other-configs '' and --cpu-full-configs '' switch parts of --full off.
 """
 from __future__ import annotations
 
@@ -64,6 +72,11 @@ def parse():
     ap.add_argument("--other-configs", default="baseline_f12_b8,more_blocks_f120_b1,more_blocks_f12_b5",
                     help="extra single-GPU legs after the headline, outside its timed region (BASELINE.json configs "
                          "2, 4 and 5 per GPU; N=1 only); '' for none")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one produced as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also: per-kernel probe (roofline, top_kernels), the --other-configs legs and the CPU leg "
+                         "(cpu_baseline, fwd_error); a plain run only times the headline")
     return ap.parse_args()
 
 
@@ -539,6 +552,25 @@ def other_leg(name, dev, probe, log):
     return res
 
 
+# ------------------------------------------------------------------------------------------------ outputs
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MiB of float32, so the three files stay far below 64 MB
+
+
+def dump_outputs(path, loss, opt):
+    """What the last timed train_step left behind, as float32 .npy files: the loss it returned and the flat
+    parameter and gradient vectors after its AdamW update.  A vector longer than DUMP_MAX_ELEMS is sampled at
+    sorted indices drawn once from a seeded generator (the same indices in every run and build)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    for name, t in (("params", opt.flat.data), ("grads", opt.flat.grad)):
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.float().cpu().numpy())
+
+
 # ------------------------------------------------------------------------------------------------ main
 def main():
     a = parse()
@@ -581,7 +613,7 @@ def main():
         feed = make_feed(a.data, B, F, H, W, dev, rank, world, a.warmup + a.steps)
         next_batch = lambda: next(feed)  # noqa: E731
 
-    probe = None if a.no_probe else KernelProbe(K)
+    probe = KernelProbe(K) if a.full and not a.no_probe else None
 
     def log(msg):
         if rank == 0:
@@ -652,6 +684,8 @@ def main():
         if world > 1:
             torch.distributed.destroy_process_group()
         return
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, loss, opt)
     samples = B * a.steps * world
     value = samples / elapsed
     tflop = train_flops_per_sample(unet.net, F, H, W) / 1e12
@@ -680,7 +714,7 @@ def main():
     if dist_info is not None:
         out["distributed"] = dist_info
     log(f"timed {a.steps} steps: {elapsed:.2f}s -> {value:.2f} samples/s")
-    if world == 1 and a.other_configs and a.dtype == "bf16":
+    if a.full and world == 1 and a.other_configs and a.dtype == "bf16":
         # BASELINE.json configs 2, 4 (per-GPU leg) and 5 (per-GPU batch), after the headline and outside its timed
         # region; the headline's model, optimizer state and batch are freed first
         del diff, opt, unet, next_batch
@@ -690,7 +724,7 @@ def main():
         out["other_configs"] = {}
         for name in [n for n in a.other_configs.split(",") if n]:
             out["other_configs"][name] = other_leg(name, dev, probe, log)
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         log("CPU leg (oracle fp32: forward error, train steps on host cores) ...")
         out["cpu_baseline"], out["fwd_error"] = cpu_leg(dev, a.cpu_full_configs)
     print(json.dumps(out), flush=True)

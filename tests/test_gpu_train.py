@@ -295,7 +295,7 @@ def test_bench_multirank_gloo_rehearsal():
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-           "--dist-backend", "gloo", "--steps", "2", "--warmup", "2", "--no-cpu-baseline", "--other-configs", "",
+           "--dist-backend", "gloo", "--steps", "2", "--warmup", "2", "--full", "--no-cpu-baseline", "--other-configs", "",
            "--batch", "1", "--height", "64", "--width", "96"]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]

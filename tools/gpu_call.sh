@@ -4,7 +4,7 @@
 # Steps (run in order; each GPU step has its own time limit, the first failure ends the call):
 #   test[:<pytest -k expr>]   pytest -m gpu (optionally -k)              -> gpurun_out/<tag>_pytest.log
 #   smoke                      __graft_entry__.smoke()                    -> gpurun_out/<tag>_smoke.log
-#   bench                      bench.py, the default contract run         -> gpurun_out/<tag>_bench.json
+#   bench                      bench.py --full (headline, other legs, CPU leg) -> <tag>_bench.json
 #   prof                       rocprofv3 --kernel-trace --stats of the headline step -> <tag>_kernel_summary.txt
 #   calls:<pattern>            per-call durations of kernels matching <pattern> in the headline step
 #   f120                       the F = 120 leg profiled (kernel totals + per-call tflash)
@@ -37,7 +37,8 @@ for step in "$@"; do
       timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "gpurun_out/${tag}_smoke.log" 2>&1
       tail -2 "gpurun_out/${tag}_smoke.log";;
     bench)
-      timeout -k 10 600 python3 bench.py > "gpurun_out/${tag}_bench.json" 2> "gpurun_out/${tag}_bench.err"
+      res=$(dirname "$(ls */"${tag}_md5.txt")")  # the results folder made above
+      timeout -k 10 600 python3 bench.py --full > "$res/${tag}_bench.json" 2> "$res/${tag}_bench.err"
       python3 -c "import json; d=json.load(open('gpurun_out/${tag}_bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['frac'], {k: v.get('ms_per_step') for k, v in d.get('other_configs', {}).items()})";;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "gpurun_out/${tag}_prof" -o run -- \
