@@ -38,7 +38,8 @@ def _flags(src: Path):
 
 def _compile(src: Path) -> Path:
     out = OBJ / (src.stem + ".o")
-    deps = [src, CSRC / "common.h", Path(__file__)]
+    # every header counts for every source (no per-source include scan): an edit to one rebuilds all
+    deps = [src, *CSRC.glob("*.h"), ROOT / "include" / "cesm_hip.h", Path(__file__)]
     if out.exists() and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, *_flags(src), "-c", str(src), "-o", str(out)]

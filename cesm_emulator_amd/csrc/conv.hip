@@ -62,7 +62,6 @@ constexpr int BK = 32;       // K per staging step (channels of one tap)
 constexpr int BMP = 128;     // pixels per block
 
 template <typename T> struct KCfg;
-template <> struct KCfg<bf16> { static constexpr int VEC = 8; static constexpr int LDW = 40; };   // 80-B rows
 template <> struct KCfg<float> { static constexpr int VEC = 4; static constexpr int LDW = 36; };  // 144-B rows
 
 // PAR (U = 2, S = 1, even KH/KW, even Ho/Wo): parity-blocked transposed conv.  Output pixels with
@@ -480,7 +479,6 @@ __global__ __launch_bounds__(256) void conv_fwd_bf16_kernel(const bf16* __restri
 // current one is consumed.  4 waves = 2 (co halves) x 2 (pixel halves of 4 rows).
 // ----------------------------------------------------------------------------------------
 constexpr int H3_TH = 8, H3_TW = 32;     // default tile (TH x TW is chosen per level, see c2_tile)
-constexpr int H3_NPIX = 384;             // max halo pixels (TH+2)(TW+2) actually staged
 constexpr int H3_P = 40;                 // LDS halo row pitch (pixels): >= TW+2, multiple of 8 (see below)
 constexpr int H3_NROW = 10 * H3_P;       // LDS halo rows ((TH+2) <= 10 tile rows of H3_P pixels)
 constexpr int H3_LD = 32;                // bf16 per LDS row: 32 channels = 64 B, no padding
@@ -577,9 +575,6 @@ __device__ __forceinline__ void h3_epilogue(const f32x4 (&acc)[NI][NJ], const in
 // overlap (profiles/r6o_tap_pair_conv_ab.txt).  Removed.  Also round 6: an L2 touch of chunk ch + 1's weight and
 // halo lines (4 B per 128-B line, LDS-direct) issued while chunk ch computes -- the step's halo conv calls 1 % faster,
 // the step 0.3 ms slower (profiles/r6late_h3_touch_ab.txt).  Removed.)
-#ifndef H3_PW
-#define H3_PW 1
-#endif
 #ifdef CESM_H3_STAMPS
 __device__ uint64_t* g_h3_stamp_buf = nullptr;
 __device__ int g_h3_stamp_blocks = 0;
@@ -598,7 +593,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(const bf16* __rest
   constexpr int NROWS = (NJv == 7 ? 16 : 10) * H3_P;
   __shared__ __attribute__((aligned(16))) bf16 sh[NROWS * H3_LD];
   // the weight tile as three arrays of 3 taps each: distinct LDS objects, so the compiler's wait insertion can see that
-  // reads of taps 0-2 do not depend on the DMA still landing taps 3-8 (H3_PW)
+  // reads of taps 0-2 do not depend on the DMA still landing taps 3-8
   __shared__ __attribute__((aligned(16))) bf16 sw0[3 * H3_BN * H3_LD];
   __shared__ __attribute__((aligned(16))) bf16 sw1[3 * H3_BN * H3_LD];
   __shared__ __attribute__((aligned(16))) bf16 sw2[3 * H3_BN * H3_LD];
@@ -621,7 +616,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(const bf16* __rest
   const int ty = tt / tiles_x, tx = tt - ty * tiles_x;
   const int y0 = ty * TH, x0 = tx * TW;
   constexpr int HWd = TW + 2;
-  const int HP = (TH + 2) * HWd;
   const int n0 = cb * H3_BN;
   const int Cin = g.C1 + g.C2;
   const int nchunk = Cin / 32;
@@ -721,17 +715,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(const bf16* __rest
     H3STAMP(0);
     stage(ch);
     H3STAMP(1);
-#if H3_PW
     // progressive landing: each wave's 9 weight pieces are the youngest, piece k = tap k; wait for the halo and taps
     // 0-2 only, and for taps 3-5 / 6-8 at the tap loop's two later barriers
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     H3STAMP(2);
     __builtin_amdgcn_s_barrier();
-#else
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    H3STAMP(2);
-    __syncthreads();
-#endif
     H3STAMP(3);
 #ifdef CESM_H3_STAMPS
     if (ch < 8) hland[ch] = h_t;
@@ -751,7 +739,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(const bf16* __rest
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const int b = tap & 1;
-      const bool gate = H3_PW && (tap == 2 || tap == 5);  // the next tap's weights land behind a barrier
+      const bool gate = tap == 2 || tap == 5;  // the next tap's weights land behind a barrier
       __builtin_amdgcn_sched_barrier(0);
       if (tap + 1 < 9 && !gate) rd(tap + 1, b ^ 1);
 #pragma unroll
@@ -880,7 +868,6 @@ __global__ __launch_bounds__(256, 2) void convs2_bf16_kernel(const bf16* __restr
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int y0 = ty * TH, x0 = tx * TW;  // tile origin on the low-resolution grid
   constexpr int HWd = TW + 2;
-  const int HP = (TH + 2) * HWd;
   const int ncob = g.Cout / H3_BN;
   const int par = UP ? (int)blockIdx.z / ncob : 0;
   const int n0 = ((int)blockIdx.z - par * ncob) * H3_BN;
@@ -1019,16 +1006,9 @@ __global__ __launch_bounds__(256, 2) void convs2_bf16_kernel(const bf16* __restr
 }
 
 // ----------------------------------------------------------------------------------------
-// 3x3 / stride 1 / pad 1 conv (bf16), v3 "wide wave": block = TH x TW (<= 512) output pixels of one
-// image x 64 output channels; 4 waves, wave w owns tile pixels [128w, 128w + 128) (8 fragment groups
-// of 16) x ALL 64 channels (32 accumulators): per tap 4 A + 8 B ds_read_b128 feed 32 MFMA (0.375
-// reads / MFMA vs 0.625 for the 32-co wave tile of conv3x3_bf16_kernel), and the block's 512 pixels
-// halve the weight staging per pixel.  Per 32-channel chunk the (TH+2)(TW+2) halo and the 9 x 64 x 32
-// weight tile are staged by LDS-DMA (global_load_lds, no VGPR round trip) into 64-B rows whose
-// 16-B chunk index is XORed with (row >> 1) & 2 - conflict-free for ds_read_b128 over any 16
-// consecutive rows (exhaustive check over the four lane groups); the weight-fragment addresses are
-// compile-time + lane constants.  76 KiB LDS -> two blocks per CU: one stages while the other
-// computes.
+// LDS image of the persistent 3x3 convs (conv3x3p_kernel, conv3x3ws_kernel): halo and weight tiles of one 32-channel
+// chunk in 64-B rows, staged by LDS-DMA in 1-KiB pieces of 16 rows; the 16-B chunk index of a row is XORed with
+// (row >> 1) & 2 -- conflict-free for ds_read_b128 over any 16 consecutive rows.
 // ----------------------------------------------------------------------------------------
 constexpr int CW_HROWS = 640;                       // max halo rows (TH+2)(TW+2)
 constexpr int CW_WROWS = 9 * 64;                    // weight rows (tap*64 + co)
@@ -1036,67 +1016,14 @@ constexpr int CW_HPIECE = CW_HROWS / 16;            // 1-KiB glds pieces
 constexpr int CW_WPIECE = CW_WROWS / 16;
 constexpr int CW_HPW = CW_HPIECE / 4;               // halo pieces per wave (10)
 constexpr int CW_WPW = CW_WPIECE / 4;               // weight pieces per wave (9)
-__device__ __attribute__((aligned(64))) bf16 cw_zero_page[32] = {};
 
 __device__ __forceinline__ int cw_swz(int row) { return (row >> 1) & 2; }
-__device__ __forceinline__ bf16x8 zero8_bf16() {
-  bf16x8 z;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) z[i] = (bf16)0.f;
-  return z;
-}
 // byte offset of 16-B chunk c (8 channels) of row `row`
 __device__ __forceinline__ int cw_off(int row, int c) { return (row << 6) + ((c ^ cw_swz(row)) << 4); }
 
-// the 9 taps of one staged 32-channel chunk: 4 A + 8 B fragments per tap, software-pipelined one
-// tap ahead in registers (the reads of tap t+1 are issued before tap t's 32 MFMAs; sched_barrier
-// pins the order so the scheduler cannot hoist every tap's reads and blow the register budget)
-template <int TW>
-__device__ __forceinline__ void cw_taps(const char* sh, const char* sw, const int (&hoff)[8], int lr, int lg,
-                                        f32x4 (&acc)[4][8]) {
-  constexpr int HWd = TW + 2;
-  bf16x8 af[2][4], bfr[2][8];
-  // weight rows tap*64 + i*16 + lr: swizzle bit = bit 2 of lr -> compile-time offset + a lane constant
-  const int a_lane = (lr << 6) + ((lg ^ cw_swz(lr)) << 4);
-  // opaque copies: keeps the (non-linear, swizzled) halo addresses from being hoisted out of the
-  // chunk loop as 72 loop-invariant VGPRs
-  int ho[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    ho[j] = hoff[j];
-    asm volatile("" : "+v"(ho[j]));
-  }
-  auto load = [&](int tap, int b) {
-    const int ky = tap / 3, kx = tap - ky * 3;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af[b][i] = *reinterpret_cast<const bf16x8*>(sw + a_lane + (tap * 64 + i * 16) * 64);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bfr[b][j] = *reinterpret_cast<const bf16x8*>(sh + cw_off(ho[j] + ky * HWd + kx, lg));
-  };
-  load(0, 0);
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap) {
-    const int b = tap & 1;
-    if (tap + 1 < 9) load(tap + 1, b ^ 1);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[b][i], bfr[b][j], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
 // ----------------------------------------------------------------------------------------
-// 3x3 conv (bf16), v4 "pipelined wide wave": the conv3x3w tile / wave layout / LDS image, but
-// persistent (one block per CU) with TWO LDS stages: the buffer-LDS-DMA of step s+1 (next 32-channel
-// chunk, or the next item's first chunk) is issued right after the barrier that opens step s and
-// lands while step s's 288 MFMAs per wave run.  Steps run over the block's items (it = blockIdx.x +
-// k * gridDim.x; item = (image, tile, 64-channel co block), co block fastest so the co blocks of a
-// tile run concurrently and share its halo in L2).
+// persistent 3x3 conv (conv3x3p_kernel) and the tap routine it shares with the warp-specialized conv
 // ----------------------------------------------------------------------------------------
-constexpr int CP_STAGE = (CW_HROWS + CW_WROWS) * 64;  // 76 KiB
 constexpr int CP_ELD = 68;                            // epilogue tile row (bf16): 136 B, conflict-free 8-B writes
 constexpr int CP_PITCH = 40;                          // halo row pitch (pixels): multiple of 8
 constexpr int CP_TH = 14;                             // max tile rows: (14 + 2) * 40 = 640 halo rows
@@ -1160,24 +1087,22 @@ __device__ __forceinline__ void cp_taps(const char* sh, const char* sw, const in
 // so concurrent launches (two streams, graph branches, two model instances) are independent.  (Round 3 claimed
 // items from a process-global atomic counter instead: 596.6 vs 599.1 us per launch, not worth the hidden state.)
 
-template <int TW, int NG, bool RW, int NST = 2, int HPW = CW_HPW>
+template <int TW>
 __global__ __launch_bounds__(256, 1) void conv3x3p_kernel(const bf16* __restrict__ x1, const bf16* __restrict__ x2,
                                                           const bf16* __restrict__ w, const float* __restrict__ bias,
                                                           const bf16* __restrict__ res, const bf16* __restrict__ res2,
                                                           bf16* __restrict__ y1, bf16* __restrict__ y2, ConvGeom g,
                                                           int tiles_x, int tiles_per_img, int TH, int ncob, int nitems,
                                                           float* __restrict__ gnp, int gn_fimg) {
-  static_assert(TW + 2 <= CP_PITCH && NG <= 8 && HPW <= CW_HPW, "tile geometry");
-  static_assert(NST == 2 || (NST == 3 && RW), "3 stages only with resident weights");
+  constexpr int NG = 7;  // fragment groups of 16 pixels per wave: 4 waves x 7 x 16 = 448 = CP_TH x 32 pixels
+  static_assert(TW + 2 <= CP_PITCH && 2 * NG == 14, "tile geometry; the vmcnt(14) / vmcnt(18) waits count 2*NG stores");
   // one LDS array (a second __shared__ object can make hipcc drain the DMA before ds_reads):
-  // 2 stages | [RW: resident weights, all chunks] | bias [Cout <= 1024] fp32.  RW (Cin = Cout = 64):
-  // a stage holds only the halo and the 2 x 36 KiB weight chunks are loaded once per block
-  // NST = 3 (RW, short tiles): every wave issues exactly HPW halo pieces per step (rows past the halo
-  // load zeros) so the step-start wait can leave the next step's pieces and the epilogue stores in
-  // flight: vmcnt(HPW + 2*NG)
-  constexpr int STG = RW ? HPW * 4 * 1024 : CP_STAGE;
-  constexpr int WRES = RW ? 2 * CW_WROWS * 64 : 0;
-  constexpr int BIASB = RW ? 256 : 4096;
+  // 2 stages | resident weights, both chunks | bias [Cout = 64] fp32.  Cin = Cout = 64: a stage holds only the
+  // halo and the 2 x 36 KiB weight chunks are loaded once per block
+  constexpr int NST = 2, HPW = CW_HPW;
+  constexpr int STG = HPW * 4 * 1024;
+  constexpr int WRES = 2 * CW_WROWS * 64;
+  constexpr int BIASB = 256;
   __shared__ __attribute__((aligned(1024))) char lds[NST * STG + WRES + BIASB + 16];
   char* wres = lds + NST * STG;
   float* sbias = reinterpret_cast<float*>(lds + NST * STG + WRES);
@@ -1185,7 +1110,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3p_kernel(const bf16* __restrict
   const int lr = lane & 15, lg = lane >> 4;
   const int HP = (TH + 2) * CP_PITCH;
   for (int c = tid; c < g.Cout; c += 256) sbias[c] = bias ? bias[c] : 0.f;
-  const int hpieces = NST == 3 ? 4 * HPW : (HP + 15) >> 4;
+  const int hpieces = (HP + 15) >> 4;
   const int Cin = g.C1 + g.C2;
   const int nchunk = Cin / 32;
   const int prow = lane >> 2, pslot = lane & 3;
@@ -1220,9 +1145,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3p_kernel(const bf16* __restrict
     y0 = ty * TH;
     x0 = (r - ty * tiles_x) * TW;
   };
-  // LDS-DMA of step s, piece by piece: piece k < CW_HPW = halo piece, else (!RW) weight piece.
-  // Source descriptors of the step being prefetched (set by step_src):
-  __amdgpu_buffer_rsrc_t dxrs, dwrs;
+  // LDS-DMA of step s, piece by piece (halo pieces only: the weights are resident).
+  // Source descriptor of the step being prefetched (set by step_src):
+  __amdgpu_buffer_rsrc_t dxrs;
   int dcs = 0, dy0 = 0, dx0 = 0;
   char* dsh = lds;
   auto step_src = [&](int s, int it, int ch) {
@@ -1235,38 +1160,26 @@ __global__ __launch_bounds__(256, 1) void conv3x3p_kernel(const bf16* __restrict
     const int64_t img_elems = (int64_t)g.Hi * g.Wi * dcs;
     dxrs = __builtin_amdgcn_make_buffer_rsrc((void*)(src + (int64_t)n * img_elems + cc), (short)0,
                                              (int)(img_elems * 2 - cc * 2), 0x00020000);
-    dwrs = __builtin_amdgcn_make_buffer_rsrc((void*)(w + ((int64_t)cob * (Cin / 32) + ch) * (9 * 64 * 32)), (short)0,
-                                             9 * 64 * 32 * 2, 0x00020000);  // chunked pack (wpk_index)
     dsh = lds + (s % NST) * STG;
   };
   auto issue_piece = [&](int k) {
-    if (k < HPW) {
-      const int q = wid + 4 * k;
-      if (q < hpieces) {  // wave-uniform
-        const int chunk = pslot ^ cw_swz(16 * q + prow);
-        const int iy = dy0 - 1 + (hrel[k] >> 16), ix = dx0 - 1 + (hrel[k] & 0xffff);
-        const bool in = hrel[k] >= 0 && (unsigned)iy < (unsigned)g.Hi && (unsigned)ix < (unsigned)g.Wi;
-        const int vo = in ? ((iy * g.Wi + ix) * dcs + chunk * 8) * 2 : 0x7ffffff0;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(dxrs, (__attribute__((address_space(3))) void*)(dsh + q * 1024), 16,
-                                                 vo, 0, 0, 0);
-      }
-    } else if constexpr (!RW) {
-      const int q = wid + 4 * (k - HPW);
-      const int row = 16 * q + prow;  // tap*64 + co
-      const int chunk = pslot ^ cw_swz(row);
-      const int vo = (row * 32 + chunk * 8) * 2;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(dwrs,
-                                               (__attribute__((address_space(3))) void*)(dsh + CW_HROWS * 64 + q * 1024),
-                                               16, vo, 0, 0, 0);
+    const int q = wid + 4 * k;
+    if (q < hpieces) {  // wave-uniform
+      const int chunk = pslot ^ cw_swz(16 * q + prow);
+      const int iy = dy0 - 1 + (hrel[k] >> 16), ix = dx0 - 1 + (hrel[k] & 0xffff);
+      const bool in = hrel[k] >= 0 && (unsigned)iy < (unsigned)g.Hi && (unsigned)ix < (unsigned)g.Wi;
+      const int vo = in ? ((iy * g.Wi + ix) * dcs + chunk * 8) * 2 : 0x7ffffff0;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(dxrs, (__attribute__((address_space(3))) void*)(dsh + q * 1024), 16,
+                                               vo, 0, 0, 0);
     }
   };
-  constexpr int NPIECE = RW ? HPW : HPW + CW_WPW;  // per wave per step
+  constexpr int NPIECE = HPW;  // per wave per step
   auto issue = [&](int s, int it, int ch) {
     step_src(s, it, ch);
 #pragma unroll
     for (int k = 0; k < NPIECE; ++k) issue_piece(k);
   };
-  if constexpr (RW) {  // the whole (64 co x 9 taps x 64 ci) weight, chunk-major, waited for by step 0
+  {  // the whole (64 co x 9 taps x 64 ci) weight, chunk-major, waited for by step 0
     const __amdgpu_buffer_rsrc_t wrs0 = __builtin_amdgcn_make_buffer_rsrc((void*)w, (short)0, 64 * 9 * 64 * 2, 0x00020000);
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch)
@@ -1288,6 +1201,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3p_kernel(const bf16* __restrict
   bool epi = false;
   int it = (int)blockIdx.x;
   for (int k = 0; it < nitems; ++k) {
+    (void)k;  // unused, but a plain `while` compiles to different code (register allocation, two instructions)
     const int nxt = it + (int)gridDim.x;
     f32x4 acc[4][NG];
 #pragma unroll
@@ -1296,52 +1210,36 @@ __global__ __launch_bounds__(256, 1) void conv3x3p_kernel(const bf16* __restrict
       for (int j = 0; j < NG; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int ch = 0; ch < nchunk; ++ch, ++s) {
       // step s landed: after an epilogue only its 2*NG stores are younger than step s's DMA
-      if constexpr (NST == 3) {
-        // steady state (nchunk == 2): younger than step s's DMA are step s+1's HPW pieces and one
-        // epilogue's 2*NG stores; the first two and the last two steps drain completely
-        static_assert(HPW + 2 * NG == 15, "vmcnt immediate below");
-        if (s >= 2 && s + 1 < nsteps && nchunk == 2) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      } else if (epi) {
+      if (epi) {
         // younger than step s's DMA: the epilogue's 2*NG output stores (+ 4 GroupNorm partial stores)
-        if (gnp) {
-          if constexpr (NG == 8) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-          else asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-        } else {
-          if constexpr (NG == 8) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-          else asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-        }
+        if (gnp) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       epi = false;
       __builtin_amdgcn_s_barrier();                     // ... for every wave; step s-1's reads are done
       const char* sh = lds + (s % NST) * STG;
-      const char* sw = RW ? wres + ch * CW_WROWS * 64 : sh + CW_HROWS * 64;
+      const char* sw = wres + ch * CW_WROWS * 64;
       const int sp = s + NST - 1;  // step prefetched now, into the stage step s-1 used
-      // its item / chunk: NST = 2: the next chunk of this item, or the next item's first chunk
-      const int sp_it = NST == 2 ? (ch + 1 < nchunk ? it : nxt) : (int)blockIdx.x + (sp / nchunk) * (int)gridDim.x;
-      const int sp_ch = NST == 2 ? (ch + 1 < nchunk ? ch + 1 : 0) : sp % nchunk;
-      const bool pf = NST == 2 ? sp_it < nitems : sp < nsteps;
-      if constexpr (!RW) {  // spreading the 19-piece (!RW) DMA over the taps spills at NG = 8
-        if (pf) issue(sp, sp_it, sp_ch);
-        cp_taps<NG>(sh, sw, bad, a_lane, acc);
-      } else {
-        // the prefetch DMA spread over this step's taps (issuing all of it up front stalls the wave on the
-        // vector-memory queue before its first MFMA).  ONE tap loop for both cases (pf is a uniform branch inside
-        // the hook): with a second, hook-less copy of the loop the compiler gave the two copies different
-        // accumulator registers and copied all 112 of them AGPR -> VGPR -> AGPR at every step (224 v_accvgpr
-        // moves per 252 MFMAs)
-        if (pf) step_src(sp, sp_it, sp_ch);
-        auto hook = [&](int tap) {
-          if (pf) {
+      // its item / chunk: the next chunk of this item, or the next item's first chunk
+      const int sp_it = ch + 1 < nchunk ? it : nxt;
+      const int sp_ch = ch + 1 < nchunk ? ch + 1 : 0;
+      const bool pf = sp_it < nitems;
+      // the prefetch DMA spread over this step's taps (issuing all of it up front stalls the wave on the
+      // vector-memory queue before its first MFMA).  ONE tap loop for both cases (pf is a uniform branch inside
+      // the hook): with a second, hook-less copy of the loop the compiler gave the two copies different
+      // accumulator registers and copied all 112 of them AGPR -> VGPR -> AGPR at every step (224 v_accvgpr
+      // moves per 252 MFMAs)
+      if (pf) step_src(sp, sp_it, sp_ch);
+      auto hook = [&](int tap) {
+        if (pf) {
 #pragma unroll
-            for (int k = 0; k < NPIECE; ++k)
-              if (k * 9 / NPIECE == tap) issue_piece(k);
-          }
-        };
-        cp_taps<NG>(sh, sw, bad, a_lane, acc, hook);
-      }
+          for (int k = 0; k < NPIECE; ++k)
+            if (k * 9 / NPIECE == tap) issue_piece(k);
+        }
+      };
+      cp_taps<NG>(sh, sw, bad, a_lane, acc, hook);
     }
     int n, y0, x0, cob;
     item_geo(it, n, y0, x0, cob);
@@ -2052,27 +1950,9 @@ __global__ __launch_bounds__(256, NS == 1 ? 4 : 2) void gemm1x1_kernel(const bf1
 
 
 // ----------------------------------------------------------------------------------------
-// 3x3 / stride 1 / pad 1 conv (bf16), v2: persistent, software-pipelined halo conv.
-// Work item = (TH x TW pixel tile of one image, 64 output channels); a block streams the
-// (item, 32-channel chunk) sequence through two LDS stages filled by global_load_lds (LDS-DMA, no
-// VGPR staging): the loads of step s+2 are issued as soon as step s's stage is released and stay in
-// flight across the raw barriers (counted s_waitcnt vmcnt).  Stage = halo [(TH+2)(TW+2) <= 384 px]
-// [32 ch] + weights [9 taps x 64 co][32 ci], 64-B rows with the 16-B chunk index XORed by
-// (row >> 2) & 3 (conflict-free fragment reads).  Generic TW lets W = 36 / 72 / 144 levels use
-// 36-wide tiles instead of wasting 25-44 % of a 32-wide tiling.  4 waves = 2 (co halves) x 2
-// (pixel halves); wave tile 32 co x 128 px, 16 MFMA per tap.
+// host-side tile choosers of the halo kernels
 // ----------------------------------------------------------------------------------------
-constexpr int C2_HROWS = 384;                 // halo rows per stage (>= (TH+2)(TW+2))
-constexpr int C2_HALO_B = C2_HROWS * 64;      // 24 KiB
-constexpr int C2_W_B = 9 * 64 * 64;           // 36 KiB
-constexpr int C2_STAGE_B = C2_HALO_B + C2_W_B;
-constexpr int C2_NI = C2_HROWS / 16 + 9 * 64 / 16;  // wave-instructions per stage (60)
-constexpr int C2_NPW = C2_NI / 4;                   // per wave (15)
-static_assert(C2_NI % 4 == 0, "glds instructions must split evenly over the 4 waves");
-__device__ __attribute__((aligned(16))) bf16 c2_zero_page[8] = {};
-
-__device__ __forceinline__ int c2_swz(int row) { return (row >> 2) & 3; }
-
+constexpr int C2_HROWS = 384;                 // most halo pixels (TH+2)(TW+2) of a c2_tile tile
 // tile shape for an Ho x Wo image: TW in {32, 36, 48}, TH*TW <= 256, (TH+2)(TW+2) <= 384; maximise
 // useful / computed pixels (fewest tiles on ties)
 static void c2_tile(int Ho, int Wo, int& TH, int& TW, bool only_32_36 = false) {
@@ -3811,6 +3691,8 @@ enum ConvFwdVariant {
   CFV_GEMM1X1_128 = 0, CFV_GEMM1X1_64, CFV_P32_RW, CFV_HALO36, CFV_HALO32, CFV_TCONV_PAR_128, CFV_TCONV_PAR_64, CFV_GEN_BF16_128, CFV_GEN_BF16_64,
   CFV_GEN_F32_128, CFV_GEN_F32_64, CFV_S2DOWN36, CFV_S2DOWN32, CFV_S2UP36, CFV_S2UP32, CFV_WS32, CFV_WS36, CFV_COUNT
 };
+// (labels that tests, bench.py and the committed profiles key on; "conv3x3p_kernel<32,7,true>" keeps the arguments
+// of the template it was before the kernel was specialised to its one instantiation)
 static const char* const kConvFwdVariantName[CFV_COUNT] = {
     "gemm1x1_kernel<128>", "gemm1x1_kernel<64>", "conv3x3p_kernel<32,7,true>", "conv3x3_bf16_kernel<36>",
     "conv3x3_bf16_kernel<32>", "conv_fwd_bf16_kernel<128,true>", "conv_fwd_bf16_kernel<64,true>",
@@ -3944,7 +3826,7 @@ int conv_fwd_launch(int dtype, const void* x1, const void* x2, const void* wp, c
       const int ncob = Cout / 64;
       const int nitems = Nb * tx * ty * ncob;
       const int nblk = std::min(nitems, cesm_num_cus());
-      conv3x3p_kernel<32, 7, true><<<nblk, 256, 0, stream>>>(bx1, bx2, bwp, bias, br, br2, by1, by2, g, tx, tx * ty, TH,
+      conv3x3p_kernel<32><<<nblk, 256, 0, stream>>>(bx1, bx2, bwp, bias, br, br2, by1, by2, g, tx, tx * ty, TH,
                                                              ncob, nitems, gnp, gn_fimg);
       break;
     }
@@ -4062,79 +3944,122 @@ int cesm_conv_fwd_gn(int dtype, const void* x1, const void* x2, const void* wp, 
 }  // extern "C"
 
 namespace {
-// Kernel selection of cesm_conv_wgrad (host only)
-enum WgradVariant { WGV_WIDE = 0, WGV_GEN, WGV_S2, WGV_W32C64, WGV_W36C64 };
-// input-channel tile of wgrad_sq_kernel for a bf16 1x1 weight gradient it takes (0: the wide kernel's 64-column
-// tiles): one source, one destination, no bias; Cout % 256 == 0 with BN = 256 when Cin % 256 == 0, else 128; or
-// Cout = 64 with Cin % 256 == 0 (64 x 256 tiles)
-static int wgrad_sq_bn(int KH, int KW, int S, int P, int U, int Hi, int Wi, int Ho, int Wo, int C1, int C2, int Cout,
-                       int Co1, bool with_bias) {
-  (void)with_bias;  // the bias gradient rides along (BIAS instantiations)
-  if (KH != 1 || KW != 1 || S != 1 || P != 0 || U != 1 || Hi != Ho || Wi != Wo || C2 != 0 || Co1 != Cout) return 0;
-  if (Cout == 64) return C1 % 256 == 0 ? 256 : 0;  // 64 x 256 tiles (the level-0 to_out: dY read once, not per 64 ci)
-  if (Cout % 256 != 0) return 0;
-  if (C1 % 256 == 0) return 256;
-  if (C1 % 128 == 0) return 128;
-  return 0;
-}
-static int wgrad_plan(int dtype, int64_t M, int Hi, int Wi, int Ho, int Wo, int KH, int KW, int S, int P, int U) {
-  const bool halo3 = dtype == CESM_DT_BF16 && KH == 3 && KW == 3 && S == 1 && P == 1 && U == 1 && Ho == Hi &&
-                     Wo == Wi;
-  // 8 x 36 tiles only where 32-wide tiles waste >= 20 % of the columns (W = 36, 72); at W = 144 / 288
-  // the 8 x 32 kernel's row-aligned K chunks are faster despite the partial last tile
-  if (halo3 && (Wo % W36_TW) == 0 && 5 * Wo <= 4 * (int)cdiv(Wo, W3_TW) * W3_TW) return WGV_W36C64;
-  if (halo3) return WGV_W32C64;  // (C1 % 64 == 0: cesm_conv_wgrad)
-  // (32-wide pixel tiles: at Wo = 36 the second tile of a row is 8/9 empty and the wide kernel is faster)
-  if (dtype == CESM_DT_BF16 && KH == 4 && KW == 4 && S == 2 && P == 1 && U == 1 && Hi == 2 * Ho && Wi == 2 * Wo &&
-      Wo >= 64)
-    return WGV_S2;
-  if (dtype == CESM_DT_BF16 && M < (1ll << 31)) return WGV_WIDE;
-  return WGV_GEN;
+// Kernel selection and launch shape of cesm_conv_wgrad (host only): the launcher and every cesm_conv_wgrad_* query go
+// through wgrad_plan, so the caller's slab, the launch and the tests see one decision.
+enum WgradVariant { WGV_WIDE = 0, WGV_SQ, WGV_GEN, WGV_S2, WGV_W32C64, WGV_W36C64 };
+
+// Target block counts of the split-K launches.  Every split writes a full fp32 [Cout][K] slab that conv_wgrad_reduce
+// reads back, so more blocks than ~2-4 per CU only adds slab traffic (round 3: 512 / 2048 blocks 144.7 / 131.2 ms per
+// step against 129.7 at 1024).  The split count fixes the summation order, and with it the bits, of every dW.
+constexpr int WG_BLOCKS = 1024;      // wide kernel with 64- / 128-row tiles, generic kernel
+constexpr int WG_BLOCKS_BIG = 512;   // wide kernel with 256-row tiles; halo / stride-2 kernels (64 co x 32 ci blocks)
+constexpr int WG_BLOCKS_SQ = 256;    // square-tile kernel (512 threads, 64 KB of LDS: two per CU) at 256 rows ...
+constexpr int WG_BLOCKS_SQ64 = 512;  // ... and at 64 rows (100 registers, two per CU)
+constexpr int WG_SPLIT_PX = 256;     // a split takes at least 256 pixels
+
+struct WgradPlan {
+  WgradVariant v = WGV_GEN;
+  int bm = 64, bn = 64;   // output tile (co rows x K columns) of the wide / square-tile kernels
+  int nsplit = 1;         // pixel splits: what a caller sizes the slabs for
+  bool bias = false;      // this launch also produces the bias gradient (with_bias and a kernel that carries it)
+  bool can_bias = false;  // a caller that wants the bias gradient should ask for it here (else: cesm_colsum)
+};
+
+static WgradPlan wgrad_plan(int dtype, int Nb, int Hi, int Wi, int C1, int C2, int Ho, int Wo, int Cout, int Co1,
+                            int KH, int KW, int S, int P, int U, bool with_bias) {
+  WgradPlan pl;
+  const bool bf = dtype == CESM_DT_BF16;
+  const int Cin = C1 + C2, K = KH * KW * Cin;
+  const int64_t M = (int64_t)Nb * Ho * Wo;
+  const bool same_hw = Ho == Hi && Wo == Wi, single = C2 == 0 && Co1 == Cout;  // one source, one destination
+  int64_t blocks = WG_BLOCKS, tiles;
+  if (bf && KH == 3 && KW == 3 && S == 1 && P == 1 && U == 1 && same_hw) {
+    // halo kernels, blocks of 64 co x 32 ci over all 9 taps (C1 % 64 == 0: cesm_conv_wgrad).  8 x 36 tiles only where
+    // 32-wide tiles waste >= 20 % of the columns (W = 36, 72); at W = 144 / 288 the 8 x 32 kernel's row-aligned K
+    // chunks are faster despite the partial last tile
+    pl.v = ((Wo % W36_TW) == 0 && 5 * Wo <= 4 * (int)cdiv(Wo, W3_TW) * W3_TW) ? WGV_W36C64 : WGV_W32C64;
+    blocks = WG_BLOCKS_BIG;
+    tiles = (int64_t)(Cout / 64) * (Cin / 32);
+  } else if (bf && KH == 4 && KW == 4 && S == 2 && P == 1 && U == 1 && Hi == 2 * Ho && Wi == 2 * Wo && Wo >= 64 &&
+             single && !with_bias) {
+    // 4x4 stride-2 (Downsample / the Upsample's weight gradient): blocks of 64 co x 32 ci x one input parity (4 taps);
+    // no concat, no split and no bias gradient (those take the wide kernel below)
+    // (32-wide pixel tiles: at Wo = 36 the second tile of a row is 8/9 empty and the wide kernel is faster)
+    pl.v = WGV_S2;
+    blocks = WG_BLOCKS_BIG;
+    tiles = (int64_t)(Cout / 64) * (Cin / 32) * 4;
+  } else {
+    // wide-tile kernel, or for fp32 / M >= 2^31 the generic one.  Square 256 (64) x bn tiles instead for the 1x1 convs
+    // whose dY the wide kernel would re-read once per 64 input channels: one source, one destination; Cout % 256 == 0
+    // with bn = 256 when Cin % 256 == 0, else 128; or Cout = 64 with Cin % 256 == 0 (the level-0 to_out)
+    const bool wide = bf && M < (1ll << 31);
+    int sq = 0;
+    if (wide && KH == 1 && KW == 1 && S == 1 && P == 0 && U == 1 && same_hw && single) {
+      if (Cout == 64) sq = C1 % 256 == 0 ? 256 : 0;
+      else if (Cout % 256 == 0) sq = C1 % 256 == 0 ? 256 : (C1 % 128 == 0 ? 128 : 0);
+    }
+    pl.v = sq ? WGV_SQ : (wide ? WGV_WIDE : WGV_GEN);
+    if (sq) {
+      pl.bm = Cout == 64 ? 64 : 256;
+      pl.bn = sq;
+      blocks = pl.bm == 64 ? WG_BLOCKS_SQ64 : WG_BLOCKS_SQ;
+    } else {
+      // (the generic kernel's tiles are 64 x 64; a bf16 launch it takes keeps the wide kernel's split count)
+      pl.bm = !bf ? 64 : (Cout % 256 == 0 && Co1 % 256 == 0) ? 256 : (Cout % 128 == 0 && Co1 % 128 == 0) ? 128 : 64;
+      blocks = pl.bm == 256 ? WG_BLOCKS_BIG : WG_BLOCKS;
+    }
+    tiles = (int64_t)std::max(1, Cout / pl.bm) * std::max(1, K / pl.bn);
+    pl.bias = with_bias && wide;
+    // (the wide kernel could also carry the bias gradient of a split destination; those layers have taken it from the
+    // column sum since round 3, and moving them would change db's summation order)
+    pl.can_bias = wide && Co1 == Cout;
+  }
+  pl.nsplit = (int)std::max<int64_t>(
+      1, std::min(blocks / std::max<int64_t>(1, tiles), std::max<int64_t>(1, M / WG_SPLIT_PX)));
+  return pl;
 }
 }  // namespace
 
 extern "C" {
 
-// input-channel tile of the square-tile 1x1 weight-gradient kernel for this shape (0: not taken); the caller sizes
-// nsplit (and the slab) for Cout/256 x Cin/BN tiles when it is non-zero
-int cesm_conv_wgrad_sq_bn(int dtype, int Nb, int Hi, int Wi, int C1, int C2, int Ho, int Wo, int Cout, int Co1, int KH,
-                          int KW, int S, int P, int U, int with_bias) {
-  const int64_t M = (int64_t)Nb * Ho * Wo;
-  if (wgrad_plan(dtype, M, Hi, Wi, Ho, Wo, KH, KW, S, P, U) != WGV_WIDE) return 0;
-  return wgrad_sq_bn(KH, KW, S, P, U, Hi, Wi, Ho, Wo, C1, C2, Cout, Co1, with_bias != 0);
-}
-
 const char* cesm_conv_wgrad_variant(int dtype, int Nb, int Hi, int Wi, int C1, int C2, int Ho, int Wo, int Cout,
                                     int Co1, int KH, int KW, int S, int P, int U, int with_bias) {
-  const int64_t M = (int64_t)Nb * Ho * Wo;
-  int wv = wgrad_plan(dtype, M, Hi, Wi, Ho, Wo, KH, KW, S, P, U);
-  if (wv == WGV_S2 && (with_bias || C2 || Co1 != Cout)) wv = WGV_WIDE;  // (cesm_conv_wgrad's fallback)
-  switch (wv) {
+  const WgradPlan pl = wgrad_plan(dtype, Nb, Hi, Wi, C1, C2, Ho, Wo, Cout, Co1, KH, KW, S, P, U, with_bias != 0);
+  switch (pl.v) {
     case WGV_W32C64: return "wgrad3x3c64_kernel";
     case WGV_W36C64: return "wgrad3x3w36c64_kernel";
     case WGV_S2: return "wgrads2_bf16_kernel";
+    case WGV_SQ: {
+      static const char* const sqn[6] = {"wgrad_sq_kernel<64,256>", "wgrad_sq_kernel<64,256,true>",
+                                         "wgrad_sq_kernel<256,256>", "wgrad_sq_kernel<256,256,true>",
+                                         "wgrad_sq_kernel<256,128>", "wgrad_sq_kernel<256,128,true>"};
+      return sqn[(pl.bm == 64 ? 0 : pl.bn == 256 ? 2 : 4) + (with_bias ? 1 : 0)];
+    }
     case WGV_WIDE: {
-      const int sq = wgrad_sq_bn(KH, KW, S, P, U, Hi, Wi, Ho, Wo, C1, C2, Cout, Co1, with_bias != 0);
-      if (sq) {
-        static const char* const sqn[6] = {"wgrad_sq_kernel<64,256>", "wgrad_sq_kernel<64,256,true>",
-                                           "wgrad_sq_kernel<256,256>", "wgrad_sq_kernel<256,256,true>",
-                                           "wgrad_sq_kernel<256,128>", "wgrad_sq_kernel<256,128,true>"};
-        return sqn[(Cout == 64 ? 0 : sq == 256 ? 2 : 4) + (with_bias ? 1 : 0)];
-      }
-      const int bm = (Cout % 256 == 0 && Co1 % 256 == 0) ? 256 : ((Cout % 128 == 0 && Co1 % 128 == 0) ? 128 : 64);
       static const char* const names[6] = {"wgrad_wide_kernel<64,false>", "wgrad_wide_kernel<64,true>",
                                            "wgrad_wide_kernel<128,false>", "wgrad_wide_kernel<128,true>",
                                            "wgrad_wide_kernel<256,false>", "wgrad_wide_kernel<256,true>"};
-      return names[(bm == 256 ? 4 : bm == 128 ? 2 : 0) + (with_bias ? 1 : 0)];
+      return names[(pl.bm == 256 ? 4 : pl.bm == 128 ? 2 : 0) + (with_bias ? 1 : 0)];
     }
     default: return dtype == CESM_DT_BF16 ? "conv_wgrad_kernel<__bf16>" : "conv_wgrad_kernel<float>";
   }
 }
 
+int cesm_conv_wgrad_nsplit(int dtype, int Nb, int Hi, int Wi, int C1, int C2, int Ho, int Wo, int Cout, int Co1, int KH,
+                           int KW, int S, int P, int U, int with_bias) {
+  return wgrad_plan(dtype, Nb, Hi, Wi, C1, C2, Ho, Wo, Cout, Co1, KH, KW, S, P, U, with_bias != 0).nsplit;
+}
+
+int cesm_conv_wgrad_bias_rides(int dtype, int Nb, int Hi, int Wi, int C1, int C2, int Ho, int Wo, int Cout, int Co1,
+                               int KH, int KW, int S, int P, int U) {
+  return wgrad_plan(dtype, Nb, Hi, Wi, C1, C2, Ho, Wo, Cout, Co1, KH, KW, S, P, U, false).can_bias ? 1 : 0;
+}
+
 // Weight gradient of the conv whose forward launch had geometry (…, KH, KW, S, P, U).
 // x = forward input (two sources), dy = forward output grad (two destinations, Co1 split).
 // Result accumulated/written into the PyTorch weight tensor `dw` ([D0][D1][1][KH][KW] with the
-// (swap, flip) mapping of the pack).  `slab` is an fp32 workspace of nsplit*Cout*K floats.
+// (swap, flip) mapping of the pack).  `slab` is an fp32 workspace of nsplit*Cout*K floats; nsplit is the caller's
+// (cesm_conv_wgrad_nsplit in the product path; any value >= 1 is correct).
 int cesm_conv_wgrad(int dtype, const void* x1, const void* x2, const void* dy1, const void* dy2, float* dw,
                     float* slab, float* db, float* bslab, int nsplit, int Nb, int Hi, int Wi, int C1, int C2, int Ho,
                     int Wo, int Cout, int Co1, int KH, int KW, int S, int P, int U, int swap, int flip, int accumulate,
@@ -4142,73 +4067,78 @@ int cesm_conv_wgrad(int dtype, const void* x1, const void* x2, const void* dy1, 
   if (db && !bslab) return CESM_EINVAL;
   const int Cin = C1 + C2;
   if ((Cin % 64) || (C1 % 64) || (Cout % 64) || (Co1 % 64) || nsplit <= 0) return CESM_EINVAL;
+  if (dtype != CESM_DT_BF16 && dtype != CESM_DT_F32) return CESM_EINVAL;
+  const WgradPlan pl = wgrad_plan(dtype, Nb, Hi, Wi, C1, C2, Ho, Wo, Cout, Co1, KH, KW, S, P, U, db != nullptr);
+  if (db && !pl.bias) return CESM_EUNSUPPORTED;  // the bias gradient rides only on the wide / square-tile kernels
   ConvGeom g{Nb, Hi, Wi, Ho, Wo, C1, C2, Cout, Co1, KH, KW, S, P, U};
   const int64_t M = (int64_t)Nb * Ho * Wo;
   const int64_t pps = cdiv(cdiv(M, nsplit), WG_BP) * WG_BP;
   const int K = KH * KW * Cin;
-  dim3 grid(Cout / 64, K / 64, nsplit);
-  const int wv = wgrad_plan(dtype, M, Hi, Wi, Ho, Wo, KH, KW, S, P, U);
-  if (wv == WGV_W36C64) {
-    const int tx = Wo / W36_TW;
-    const int ntiles = Nb * tx * (int)cdiv(Ho, W36_TH);
-    dim3 g3(Cout / 64, Cin / 64, std::min(nsplit, ntiles));
-    wgrad3x3w36c64_kernel<<<g3, WG_NT, 0, stream>>>((const bf16*)x1, (const bf16*)x2, (const bf16*)dy1,
-                                                  (const bf16*)dy2, slab, g, tx, ntiles);
-    nsplit = (int)g3.z;
-  } else if (wv == WGV_W32C64) {
-    const int tx = (int)cdiv(Wo, W3_TW);
-    const int ntiles = Nb * tx * (int)cdiv(Ho, W3_TH);
-    dim3 g3(Cout / 64, Cin / 64, std::min(nsplit, ntiles));
-    wgrad3x3c64_kernel<<<g3, WG_NT, 0, stream>>>((const bf16*)x1, (const bf16*)x2, (const bf16*)dy1,
-                                               (const bf16*)dy2, slab, g, tx, ntiles);
-    nsplit = (int)g3.z;
-  } else if (wv == WGV_S2 && C2 == 0 && Co1 == Cout && !db) {
-    const int tx = (int)cdiv(Wo, W3_TW);
-    const int ntiles = Nb * tx * (int)cdiv(Ho, W3_TH);
-    dim3 g3(Cout / 64, (Cin / 32) * 4, std::min(nsplit, ntiles));
-    wgrads2_bf16_kernel<<<g3, 256, 0, stream>>>((const bf16*)x1, (const bf16*)dy1, slab, g, tx, ntiles);
-    nsplit = (int)g3.z;
-  } else if (wv == WGV_WIDE && wgrad_sq_bn(KH, KW, S, P, U, Hi, Wi, Ho, Wo, C1, C2, Cout, Co1, db != nullptr) > 0) {
-    // square 256 x BN tiles for the 1x1 convs whose dY would be re-read once per 64 input channels (the caller sized
-    // nsplit for these tiles: cesm_conv_wgrad_sq_bn)
-    const int bn = wgrad_sq_bn(KH, KW, S, P, U, Hi, Wi, Ho, Wo, C1, C2, Cout, Co1, db != nullptr);
-    const int bm = Cout % 256 == 0 ? 256 : 64;
-    const dim3 gq(Cout / bm, Cin / bn, nsplit);
-    const bf16 *qx = (const bf16*)x1, *qy = (const bf16*)dy1;
+  switch (pl.v) {
+    case WGV_W36C64: {
+      const int tx = Wo / W36_TW;
+      const int ntiles = Nb * tx * (int)cdiv(Ho, W36_TH);
+      dim3 g3(Cout / 64, Cin / 64, std::min(nsplit, ntiles));
+      wgrad3x3w36c64_kernel<<<g3, WG_NT, 0, stream>>>((const bf16*)x1, (const bf16*)x2, (const bf16*)dy1,
+                                                    (const bf16*)dy2, slab, g, tx, ntiles);
+      nsplit = (int)g3.z;
+      break;
+    }
+    case WGV_W32C64: {
+      const int tx = (int)cdiv(Wo, W3_TW);
+      const int ntiles = Nb * tx * (int)cdiv(Ho, W3_TH);
+      dim3 g3(Cout / 64, Cin / 64, std::min(nsplit, ntiles));
+      wgrad3x3c64_kernel<<<g3, WG_NT, 0, stream>>>((const bf16*)x1, (const bf16*)x2, (const bf16*)dy1,
+                                                 (const bf16*)dy2, slab, g, tx, ntiles);
+      nsplit = (int)g3.z;
+      break;
+    }
+    case WGV_S2: {
+      const int tx = (int)cdiv(Wo, W3_TW);
+      const int ntiles = Nb * tx * (int)cdiv(Ho, W3_TH);
+      dim3 g3(Cout / 64, (Cin / 32) * 4, std::min(nsplit, ntiles));
+      wgrads2_bf16_kernel<<<g3, 256, 0, stream>>>((const bf16*)x1, (const bf16*)dy1, slab, g, tx, ntiles);
+      nsplit = (int)g3.z;
+      break;
+    }
+    case WGV_SQ: {
+      const dim3 gq(Cout / pl.bm, Cin / pl.bn, nsplit);
+      const bf16 *qx = (const bf16*)x1, *qy = (const bf16*)dy1;
 #define SQL(BMv, BNv, Bv) \
   wgrad_sq_kernel<BMv, BNv, Bv><<<gq, 512, 0, stream>>>(qx, qy, slab, bslab, (int)M, Cout, Cin, (int)pps)
-    if (bm == 64) { if (db) SQL(64, 256, true); else SQL(64, 256, false); }
-    else if (bn == 256) { if (db) SQL(256, 256, true); else SQL(256, 256, false); }
-    else { if (db) SQL(256, 128, true); else SQL(256, 128, false); }
+      if (pl.bm == 64) { if (db) SQL(64, 256, true); else SQL(64, 256, false); }
+      else if (pl.bn == 256) { if (db) SQL(256, 256, true); else SQL(256, 256, false); }
+      else { if (db) SQL(256, 128, true); else SQL(256, 128, false); }
 #undef SQL
-    if (db) colsum_final_kernel<<<Cout, 64, 0, stream>>>(bslab, db, nsplit, Cout, 1);
-  } else if (wv == WGV_WIDE || wv == WGV_S2) {
-    // wide-tile kernel; nsplit from the caller sized the slab for 64-row tiles, keep it
-    const int bm = (Cout % 256 == 0 && Co1 % 256 == 0) ? 256 : ((Cout % 128 == 0 && Co1 % 128 == 0) ? 128 : 64);
-    const int gx = Cout / bm, gy = (int)(K / 64);
-    const dim3 gw(gx, gy, nsplit);
-    auto launch = [&](auto bmc, auto biasc) {
-      constexpr int BMv = decltype(bmc)::value;
-      constexpr bool Bv = decltype(biasc)::value;
-      wgrad_wide_kernel<BMv, Bv><<<gw, 256, 0, stream>>>((const bf16*)x1, (const bf16*)x2, (const bf16*)dy1,
-                                                         (const bf16*)dy2, slab, bslab, g, (int)M, (int)pps);
-    };
-    using T0 = std::false_type;
-    using T1 = std::true_type;
-    if (bm == 256) { if (db) launch(std::integral_constant<int, 256>{}, T1{}); else launch(std::integral_constant<int, 256>{}, T0{}); }
-    else if (bm == 128) { if (db) launch(std::integral_constant<int, 128>{}, T1{}); else launch(std::integral_constant<int, 128>{}, T0{}); }
-    else { if (db) launch(std::integral_constant<int, 64>{}, T1{}); else launch(std::integral_constant<int, 64>{}, T0{}); }
-    if (db) colsum_final_kernel<<<Cout, 64, 0, stream>>>(bslab, db, nsplit, Cout, 1);
-  } else if (db) {
-    return CESM_EUNSUPPORTED;  // the bias gradient rides only on the wide kernel (callers use cesm_colsum)
-  } else if (dtype == CESM_DT_BF16)
-    conv_wgrad_kernel<bf16><<<grid, 256, 0, stream>>>((const bf16*)x1, (const bf16*)x2, (const bf16*)dy1,
-                                                      (const bf16*)dy2, slab, g, M, pps);
-  else if (dtype == CESM_DT_F32)
-    conv_wgrad_kernel<float><<<grid, 256, 0, stream>>>((const float*)x1, (const float*)x2, (const float*)dy1,
-                                                       (const float*)dy2, slab, g, M, pps);
-  else
-    return CESM_EINVAL;
+      break;
+    }
+    case WGV_WIDE: {
+      const dim3 gw(Cout / pl.bm, K / 64, nsplit);
+      auto launch = [&](auto bmc, auto biasc) {
+        constexpr int BMv = decltype(bmc)::value;
+        constexpr bool Bv = decltype(biasc)::value;
+        wgrad_wide_kernel<BMv, Bv><<<gw, 256, 0, stream>>>((const bf16*)x1, (const bf16*)x2, (const bf16*)dy1,
+                                                           (const bf16*)dy2, slab, bslab, g, (int)M, (int)pps);
+      };
+      using T0 = std::false_type;
+      using T1 = std::true_type;
+      if (pl.bm == 256) { if (db) launch(std::integral_constant<int, 256>{}, T1{}); else launch(std::integral_constant<int, 256>{}, T0{}); }
+      else if (pl.bm == 128) { if (db) launch(std::integral_constant<int, 128>{}, T1{}); else launch(std::integral_constant<int, 128>{}, T0{}); }
+      else { if (db) launch(std::integral_constant<int, 64>{}, T1{}); else launch(std::integral_constant<int, 64>{}, T0{}); }
+      break;
+    }
+    case WGV_GEN: {
+      dim3 grid(Cout / 64, K / 64, nsplit);
+      if (dtype == CESM_DT_BF16)
+        conv_wgrad_kernel<bf16><<<grid, 256, 0, stream>>>((const bf16*)x1, (const bf16*)x2, (const bf16*)dy1,
+                                                          (const bf16*)dy2, slab, g, M, pps);
+      else
+        conv_wgrad_kernel<float><<<grid, 256, 0, stream>>>((const float*)x1, (const float*)x2, (const float*)dy1,
+                                                           (const float*)dy2, slab, g, M, pps);
+      break;
+    }
+  }
+  if (db) colsum_final_kernel<<<Cout, 64, 0, stream>>>(bslab, db, nsplit, Cout, 1);
   const int64_t total = (int64_t)Cout * K;
   conv_wgrad_reduce_kernel<<<(unsigned)cdiv(total, 64), 256, 0, stream>>>(slab, dw, nsplit, Cout, Cin, KH, KW, swap,
                                                                           flip, accumulate);
@@ -4226,6 +4156,13 @@ int cesm_conv_pack(int dtype, const float* w, void* wp, int Cout, int Cin, int K
   else
     return CESM_EINVAL;
   return cesm_launch_status();
+}
+
+// blocks (tiles) of one cesm_conv_pack_batch job; a tile's taps x 64 channels must fit the LDS tile
+int cesm_conv_pack_blocks(int Cout, int Cin, int KH, int KW) {
+  const int T = KH * KW;
+  if (Cout <= 0 || Cin <= 0 || KH <= 0 || KW <= 0 || T > PB_TILE / PB_CI) return CESM_EINVAL;
+  return (int)(cdiv(Cout, pb_co_t(T)) * cdiv(Cin, PB_CI));
 }
 
 int cesm_conv_pack_batch(int dtype, const int64_t* jobs, int njobs, int nblocks, hipStream_t stream) {

@@ -65,16 +65,19 @@ def conv_pack_into(w, out, cout, cin, kh, kw, swap, flip):
 
 
 def pack_blocks(cout, cin, kh, kw):
-    """blocks cesm_conv_pack_batch gives one job: (co, ci) tiles of pb_co_t(T) rows x 64 channels (csrc/conv.hip)"""
-    T = kh * kw
-    cot = min(64, max(1, 4096 // (T * 64)))
-    return -(-cout // cot) * -(-cin // 64)
+    """blocks cesm_conv_pack_batch gives one job (host-only query; the kernel's own tiling, csrc/conv.hip)"""
+    n = lib().cesm_conv_pack_blocks(int(cout), int(cin), int(kh), int(kw))
+    if n < 0:
+        raise ValueError(f"conv pack job {cout} x {cin} x {kh} x {kw}: more than 64 taps (or an empty weight) does not "
+                         "fit cesm_conv_pack_batch's tile")
+    return n
 
 
 def conv_pack_table(rows, device):
     """device job table of cesm_conv_pack_batch: rows [src ptr, dst ptr, Cout, Cin, KH, KW, swap, flip], then the
     per-job block starts (exclusive prefix of pack_blocks), then the job index of every block; returns (table, nblocks)"""
-    assert len(rows) > 0 and all(r[4] * r[5] <= 64 for r in rows)  # a tile's taps x 64 channels fit the LDS tile
+    if not rows:
+        raise ValueError("conv_pack_table: no jobs")
     starts, bjob = [0], []
     for j, r in enumerate(rows):
         n = pack_blocks(r[2], r[3], r[4], r[5])
@@ -200,35 +203,10 @@ def qkv_bwd(dy, x, wt, dw, accumulate=True):
 CONV_TRACE = [] if os.environ.get("CESM_TRACE_CONV") else None
 
 
-# target block count of the split-K weight-gradient launches: every split writes a full fp32
-# [Cout][K] slab that conv_wgrad_reduce reads back, so more blocks than ~2-4 per CU only adds slab
-# traffic (round 3: 512 / 2048 blocks 144.7 / 131.2 ms per step against 129.7 at 1024)
-WGRAD_BLOCKS = 1024
-# blocks of the square-tile 1x1 weight-gradient kernel (512 threads, 64 KB of LDS: two per CU)
-WGRAD_SQ_BLOCKS = 256
-
-
-def _wgrad_nsplit(M, cout, K, bm=64, blocks=None):
-    """pixel splits of the weight-gradient GEMM: ~`blocks` blocks of (bm x 64) tiles, >= 256 pixels each"""
-    tiles = max(1, cout // bm) * max(1, K // 64)
-    n = max(1, (blocks or WGRAD_BLOCKS) // tiles)
-    n = min(n, max(1, M // 256))
-    return n
-
-
-def _wgrad_bm(x, cout, co1):
-    if x.dtype != torch.bfloat16:
-        return 64
-    if cout % 256 == 0 and co1 % 256 == 0:
-        return 256
-    if cout % 128 == 0 and co1 % 128 == 0:
-        return 128
-    return 64
-
-
 def conv_wgrad(x1, x2, dy1, dy2, dw, geom, swap, flip, accumulate=True, db=None):
-    """dW of a conv (split-K over pixels + reduce).  db: also the bias gradient (+=) in the same pass when
-    the bf16 wide-tile kernel runs; returns True if db was produced (else the caller runs colsum)."""
+    """dW of a conv (split-K over pixels + reduce).  db: also the bias gradient (+=) in the same pass when the kernel
+    for this shape carries it (cesm_conv_wgrad_bias_rides); returns True if db was produced (else the caller runs
+    colsum).  The split count, and with it dW's summation order, is the library's (cesm_conv_wgrad_nsplit)."""
     Ho, Wo, Cout, KH, KW, St, Pd, U = geom
     Nb, Hi, Wi, C1 = x1.shape
     C2 = 0 if x2 is None else x2.shape[3]
@@ -236,43 +214,20 @@ def conv_wgrad(x1, x2, dy1, dy2, dw, geom, swap, flip, accumulate=True, db=None)
     _chk(dy1, (Nb, Ho, Wo, Co1), x1.dtype)
     _chk(dy2, None if dy2 is None else (Nb, Ho, Wo, Cout - Co1), x1.dtype)
     _chk(dw, dtype=torch.float32)
-    K = KH * KW * (C1 + C2)
-    M = Nb * Ho * Wo
-    halo3 = KH == 3 and KW == 3 and St == 1 and Pd == 1 and U == 1
-    # 4x4 stride-2 (Downsample / the Upsample's weight gradient): wgrads2 kernel, blocks of 64 co x 32 ci x one
-    # input parity (4 taps); its bias gradient is the caller's column sum (same condition as cesm_conv_wgrad)
-    s2 = (KH == 4 and KW == 4 and St == 2 and Pd == 1 and U == 1 and Hi == 2 * Ho and Wi == 2 * Wo and Wo >= 64
-          and x2 is None
-          and dy2 is None and x1.dtype == torch.bfloat16)
-    if (halo3 or s2) and x1.dtype == torch.bfloat16:
-        # halo wgrad kernels: blocks of 64 co x 32 ci (all 9 taps / one parity's 4), split over pixel tiles
-        nb = WGRAD_BLOCKS // 2
-        nsplit = max(1, min(nb // max(1, (Cout // 64) * ((C1 + C2) // 32) * (4 if s2 else 1)), max(1, M // 256)))
-    else:
-        sq = lib().cesm_conv_wgrad_sq_bn(dtcode(x1), Nb, Hi, Wi, C1, C2, Ho, Wo, Cout, Co1, KH, KW, St, Pd, U,
-                                         int(db is not None))
-        if sq:
-            # square-tile 1x1 kernel: 512-thread blocks of 256 (or 64) x sq, ~WGRAD_SQ_BLOCKS of them (twice as many
-            # 64-row blocks: 100 registers, two per CU)
-            nb = WGRAD_SQ_BLOCKS * (2 if Cout == 64 else 1)
-            nsplit = max(1, min(nb // (max(1, Cout // 256) * (K // sq)), max(1, M // 256)))
-        else:
-            bm = _wgrad_bm(x1, Cout, Co1)
-            nsplit = _wgrad_nsplit(M, Cout, K, bm, WGRAD_BLOCKS // 2 if bm == 256 else WGRAD_BLOCKS)
-    slab = empty((nsplit, Cout, K), torch.float32, x1.device)
-    if CONV_TRACE is not None:
-        CONV_TRACE.append(("wgrad", Nb, Hi, Wi, C1 + C2, Ho, Wo, Cout, KH, KW, St, Pd, U))
-    # the bias rides on the wide-tile kernel only (same dispatch condition as cesm_conv_wgrad)
-    wide = x1.dtype == torch.bfloat16 and not halo3 and not s2 and M < (1 << 31) and dy2 is None
-    if db is not None and wide:
+    geo = (dtcode(x1), Nb, Hi, Wi, C1, C2, Ho, Wo, Cout, Co1, KH, KW, St, Pd, U)
+    if db is not None and not lib().cesm_conv_wgrad_bias_rides(*geo):
+        db = None
+    nsplit = lib().cesm_conv_wgrad_nsplit(*geo, int(db is not None))
+    slab = empty((nsplit, Cout, KH * KW * (C1 + C2)), torch.float32, x1.device)
+    bslab = None
+    if db is not None:
         _chk(db, (Cout,), torch.float32)
         bslab = empty((nsplit, Cout), torch.float32, x1.device)
-    else:
-        db = bslab = None
+    if CONV_TRACE is not None:
+        CONV_TRACE.append(("wgrad", Nb, Hi, Wi, C1 + C2, Ho, Wo, Cout, KH, KW, St, Pd, U))
     call("cesm_conv_wgrad", dtcode(x1), P(x1), P(x2), P(dy1), P(dy2), P(dw), P(slab), P(db), P(bslab), nsplit, Nb,
          Hi, Wi, C1, C2, Ho, Wo, Cout, Co1, KH, KW, St, Pd, U, int(swap), int(flip), int(accumulate), S())
     return db is not None
-
 
 
 def colsum(x, dst, accumulate=True):

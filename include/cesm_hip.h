@@ -36,8 +36,10 @@ extern "C" {
  *   6 (round 6): cesm_tblock_bwd_dw lost `dwout` again (the in-kernel to_out weight gradient measured slower than the
  *     forward's O write and was removed) and gained `o` after dx (O emitted by the backward); cesm_conv_pack_batch's
  *     job table gained per-job block starts and its fourth argument is the grid size;
- *     cesm_qkv_bwd / cesm_qkv_bwd_streams added. */
-#define CESM_ABI_VERSION 6
+ *     cesm_qkv_bwd / cesm_qkv_bwd_streams added;
+ *   7: cesm_conv_wgrad_sq_bn removed; cesm_conv_wgrad_nsplit, cesm_conv_wgrad_bias_rides and cesm_conv_pack_blocks
+ *     added (host-only queries: the weight-gradient split count and the pack tiling now come from the library). */
+#define CESM_ABI_VERSION 7
 int cesm_abi_version(void);
 /* Measurement aid, not a training op: nblk blocks that each occupy one whole CU (full LDS) for `usec` microseconds on
  * `stream` -- the one-GPU stand-in for the RCCL kernels of an overlapped gradient all-reduce (tools/overlap_sim.py,
@@ -68,17 +70,25 @@ int cesm_conv_fwd_gn(int dtype, const void* x1, const void* x2, const void* wp, 
  * launcher itself selects through the same function).  "invalid" if cesm_conv_fwd would return EINVAL. */
 const char* cesm_conv_fwd_variant(int dtype, int Nb, int Hi, int Wi, int C1, int C2, int Ho, int Wo, int Cout,
                                   int Co1, int KH, int KW, int S, int P, int U);
-/* Input-channel tile (256 / 128) of the square-tile 1x1 weight-gradient kernel cesm_conv_wgrad runs for this shape, 0 if
- * it runs another kernel (host-only query).  When non-zero the caller sizes nsplit for Cout/256 x Cin/BN tiles. */
-int cesm_conv_wgrad_sq_bn(int dtype, int Nb, int Hi, int Wi, int C1, int C2, int Ho, int Wo, int Cout, int Co1, int KH,
-                          int KW, int S, int P, int U, int with_bias);
-/* name of the kernel cesm_conv_wgrad launches (host-only query; with_bias: db != NULL) */
+/* Host-only queries on cesm_conv_wgrad's launch plan (no GPU work; the launcher decides through the same function;
+ * with_bias: db != NULL).  _variant: name of the kernel it launches.  _nsplit: the pixel-split count to size slab and
+ * bslab for -- it fixes the summation order of dW, so callers take it from here instead of a formula of their own.
+ * _bias_rides: 1 if the kernel chosen without a bias request can produce db in the same pass -- then pass db (and ask
+ * _nsplit / _variant with with_bias = 1); 0: leave db NULL and take the bias gradient from cesm_colsum. */
 const char* cesm_conv_wgrad_variant(int dtype, int Nb, int Hi, int Wi, int C1, int C2, int Ho, int Wo, int Cout,
                                     int Co1, int KH, int KW, int S, int P, int U, int with_bias);
+int cesm_conv_wgrad_nsplit(int dtype, int Nb, int Hi, int Wi, int C1, int C2, int Ho, int Wo, int Cout, int Co1, int KH,
+                           int KW, int S, int P, int U, int with_bias);
+int cesm_conv_wgrad_bias_rides(int dtype, int Nb, int Hi, int Wi, int C1, int C2, int Ho, int Wo, int Cout, int Co1,
+                               int KH, int KW, int S, int P, int U);
 /* weight gradient of a cesm_conv_fwd launch; written in PyTorch layout [D0][D1][1][KH][KW] with the
- * (swap, flip) mapping of cesm_conv_pack.  slab: nsplit*Cout*KH*KW*(C1+C2) floats.
+ * (swap, flip) mapping of cesm_conv_pack.  slab: nsplit*Cout*KH*KW*(C1+C2) floats; any nsplit >= 1 is accepted
+ * (cesm_conv_wgrad_nsplit gives the tuned one).
  * db (nullable): the conv bias gradient sum_px dY (+=), computed in the same pass (bslab: nsplit*Cout
- * floats); only on the bf16 wide-tile path (non-3x3, no dy2) — CESM_EUNSUPPORTED otherwise. */
+ * floats); only on the bf16 wide / square-tile kernels — CESM_EUNSUPPORTED otherwise, before anything is launched.
+ * cesm_conv_wgrad_bias_rides is narrower on purpose: it also answers 0 for a split destination (Co1 != Cout), where
+ * a db passed here would still be computed by the wide kernel; the product path takes that bias gradient from
+ * cesm_colsum, as it always has, so db's summation order stays what it was. */
 int cesm_conv_wgrad(int dtype, const void* x1, const void* x2, const void* dy1, const void* dy2, float* dw,
                     float* slab, float* db, float* bslab, int nsplit, int Nb, int Hi, int Wi, int C1, int C2, int Ho,
                     int Wo, int Cout, int Co1, int KH, int KW, int S, int P, int U, int swap, int flip, int accumulate,
@@ -93,10 +103,12 @@ int cesm_conv_pack(int dtype, const float* w, void* wp, int Cout, int Cin, int K
                    hipStream_t stream);
 /* every cached pack of one dtype redone in ONE launch after an optimizer step: jobs = device
  * int64[njobs][8] {src fp32 ptr, dst ptr, Cout, Cin, KH, KW, swap, flip} (cesm_conv_pack semantics) followed by
- * int64[njobs + 1] block starts, the exclusive prefix sum of the per-job tile counts cdiv(Cout, cot) * cdiv(Cin, 64)
- * with cot = clamp(4096 / (KH * KW * 64), 1, 64), then int64[starts[njobs]] the job index of every block; nblocks = the grid
- * (the last start is the work; any nblocks >= 1 is correct).  ABI 6: the table gained the starts, the fourth
- * argument was blocks_per_job. */
+ * int64[njobs + 1] block starts, the exclusive prefix sum of the per-job tile counts (cesm_conv_pack_blocks, host
+ * only: cdiv(Cout, cot) * cdiv(Cin, 64) with cot = clamp(4096 / (KH * KW * 64), 1, 64); CESM_EINVAL if KH * KW > 64 --
+ * a tile's taps x 64 channels must fit the kernel's 4096-float LDS tile, so such a job cannot be in the table), then
+ * int64[starts[njobs]] the job index of every block; nblocks = the grid (the last start is the work; any nblocks >= 1
+ * is correct).  ABI 6: the table gained the starts, the fourth argument was blocks_per_job. */
+int cesm_conv_pack_blocks(int Cout, int Cin, int KH, int KW);
 int cesm_conv_pack_batch(int dtype, const int64_t* jobs, int njobs, int nblocks, hipStream_t stream);
 /* dst[c] (+)= sum over rows of x[r][c]  (conv bias gradients) ; part: nsplit*C floats */
 int cesm_colsum(int dtype, const void* x, float* dst, float* part, int nsplit, int64_t rows, int C, int accumulate,

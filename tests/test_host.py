@@ -194,6 +194,88 @@ def test_bench_shape_dispatch_table():
     assert K.conv_fwd_variant(bf, N, 8, 8, 48, 0, 8, 8, 64, 64, 3, 3, 1, 1, 1) == "invalid"
 
 
+# dtype, Nb, Hi, Wi, C1, C2, Ho, Wo, Cout, Co1, KH, KW, S, P, U, want_bias -> nsplit, bias rides, kernel.  Recorded from
+# the formula kernels.conv_wgrad carried before the split count moved into the library (ABI 7); the split count fixes
+# the summation order, and so the bits, of every dW.
+_BF, _F32 = torch.bfloat16, torch.float32
+WGRAD_PLAN_TABLE = [
+    (_BF, 96, 192, 288, 64, 0, 192, 288, 64, 64, 3, 3, 1, 1, 1, 0, 256, 0, "wgrad3x3c64_kernel"),
+    (_BF, 96, 192, 288, 64, 64, 192, 288, 64, 64, 3, 3, 1, 1, 1, 0, 128, 0, "wgrad3x3c64_kernel"),
+    (_BF, 96, 24, 36, 512, 0, 24, 36, 512, 512, 3, 3, 1, 1, 1, 0, 4, 0, "wgrad3x3w36c64_kernel"),
+    (_BF, 96, 48, 72, 256, 256, 48, 72, 256, 256, 3, 3, 1, 1, 1, 0, 8, 0, "wgrad3x3w36c64_kernel"),
+    (_BF, 96, 192, 288, 64, 0, 192, 288, 768, 768, 1, 1, 1, 0, 1, 0, 170, 0, "wgrad_wide_kernel<256,false>"),
+    (_BF, 96, 96, 144, 128, 0, 96, 144, 768, 768, 1, 1, 1, 0, 1, 0, 85, 0, "wgrad_sq_kernel<256,128>"),
+    (_BF, 96, 24, 36, 512, 0, 24, 36, 768, 768, 1, 1, 1, 0, 1, 1, 42, 1, "wgrad_sq_kernel<256,256,true>"),
+    (_BF, 96, 192, 288, 256, 0, 192, 288, 64, 64, 1, 1, 1, 0, 1, 1, 512, 1, "wgrad_sq_kernel<64,256,true>"),
+    (_BF, 96, 192, 288, 64, 0, 96, 144, 64, 64, 4, 4, 2, 1, 1, 0, 64, 0, "wgrads2_bf16_kernel"),
+    # stride 2 with a bias gradient wanted: the stride-2 kernel still runs, the bias comes from the column sum
+    (_BF, 96, 192, 288, 64, 0, 96, 144, 64, 64, 4, 4, 2, 1, 1, 1, 64, 0, "wgrads2_bf16_kernel"),
+    (_BF, 96, 48, 72, 256, 0, 24, 36, 256, 256, 4, 4, 2, 1, 1, 0, 8, 0, "wgrad_wide_kernel<256,false>"),
+    (_BF, 96, 96, 144, 128, 64, 96, 144, 128, 128, 1, 1, 1, 0, 1, 1, 341, 1, "wgrad_wide_kernel<128,true>"),
+    # split destination: the bias does not ride
+    (_BF, 96, 96, 144, 128, 0, 96, 144, 128, 64, 1, 1, 1, 0, 1, 1, 256, 0, "wgrad_wide_kernel<64,false>"),
+    (_BF, 2, 8, 8, 64, 0, 8, 8, 64, 64, 3, 3, 1, 1, 1, 0, 1, 0, "wgrad3x3c64_kernel"),
+    (_BF, 1, 16, 16, 64, 0, 16, 16, 128, 128, 1, 1, 1, 0, 1, 1, 1, 1, "wgrad_wide_kernel<128,true>"),
+    (_F32, 4, 16, 16, 64, 0, 16, 16, 64, 64, 3, 3, 1, 1, 1, 1, 4, 0, "conv_wgrad_kernel<float>"),
+    (_F32, 4, 16, 16, 64, 0, 16, 16, 128, 128, 1, 1, 1, 0, 1, 0, 4, 0, "conv_wgrad_kernel<float>"),
+    # the remaining weight-gradient rows of test_bench_shape_dispatch_table
+    (_BF, 96, 48, 72, 256, 0, 48, 72, 768, 768, 1, 1, 1, 0, 1, 0, 85, 0, "wgrad_sq_kernel<256,256>"),
+    (_BF, 96, 24, 36, 512, 0, 24, 36, 768, 768, 1, 1, 1, 0, 1, 0, 42, 0, "wgrad_sq_kernel<256,256>"),
+    (_BF, 96, 192, 288, 256, 0, 192, 288, 64, 64, 1, 1, 1, 0, 1, 0, 512, 0, "wgrad_sq_kernel<64,256>"),
+    # levels 1 / 2 3x3, the level-1 Downsample, the level-0 concat res_conv with its bias
+    (_BF, 96, 96, 144, 128, 0, 96, 144, 128, 128, 3, 3, 1, 1, 1, 0, 64, 0, "wgrad3x3c64_kernel"),
+    (_BF, 96, 48, 72, 256, 0, 48, 72, 256, 256, 3, 3, 1, 1, 1, 0, 16, 0, "wgrad3x3w36c64_kernel"),
+    (_BF, 96, 96, 144, 128, 0, 48, 72, 128, 128, 4, 4, 2, 1, 1, 0, 16, 0, "wgrads2_bf16_kernel"),
+    (_BF, 96, 192, 288, 64, 64, 192, 288, 64, 64, 1, 1, 1, 0, 1, 1, 512, 1, "wgrad_wide_kernel<64,true>"),
+]
+# cesm_conv_wgrad_bias_rides for each row above, whether or not the row wants the bias (the earlier formula's `wide`: bf16,
+# not a halo or stride-2 kernel shape, one destination)
+WGRAD_CAN_RIDE = [0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 1, 1, 0, 0, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1]
+
+
+def test_wgrad_plan_table():
+    """(split count, whether the bias gradient rides, kernel) of cesm_conv_wgrad's plan as kernels.conv_wgrad asks for
+    it: db is passed only where cesm_conv_wgrad_bias_rides says so, and the split count and the kernel are those of
+    the launch that then happens"""
+    from cesm_emulator_amd import kernels as K
+    from cesm_emulator_amd._lib import lib
+    assert len(WGRAD_CAN_RIDE) == len(WGRAD_PLAN_TABLE)
+    for row, can in zip(WGRAD_PLAN_TABLE, WGRAD_CAN_RIDE):
+        dt, geo, want_bias, want = row[0], row[1:15], row[15], row[16:]
+        assert lib().cesm_conv_wgrad_bias_rides(K._DT[dt], *geo) == can, row
+        rides = int(bool(want_bias) and bool(can))
+        got = (lib().cesm_conv_wgrad_nsplit(K._DT[dt], *geo, rides), rides,
+               K.conv_wgrad_variant(dt, *geo, with_bias=bool(rides)))
+        assert got == want, (row, got)
+
+
+def test_wgrad_bias_request_unsupported():
+    """cesm_conv_wgrad with db for a shape whose kernel cannot carry the bias gradient (3x3 halo, fp32) returns
+    CESM_EUNSUPPORTED before any launch (so this needs no GPU and the pointers are never read); db without bslab is
+    CESM_EINVAL"""
+    from cesm_emulator_amd._lib import lib
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf)
+    halo = (8, 16, 16, 64, 0, 16, 16, 64, 64, 3, 3, 1, 1, 1)  # Nb .. U
+    for dt in (0, 1):
+        assert lib().cesm_conv_wgrad(dt, p, None, p, None, p, p, p, p, 1, *halo, 0, 0, 0, None) == -2
+    assert lib().cesm_conv_wgrad(1, p, None, p, None, p, p, p, None, 1, *halo, 0, 0, 0, None) == -1
+
+
+def test_conv_pack_table_guard():
+    """a pack job whose taps do not fit cesm_conv_pack_batch's LDS tile (KH * KW > 64) is refused on the host, before
+    any device use; the per-job block counts are the kernel's own (cesm_conv_pack_blocks)"""
+    from cesm_emulator_amd import kernels as K
+    with pytest.raises(ValueError):
+        K.conv_pack_table([[0, 0, 64, 64, 9, 9, 0, 0]], "cpu")
+    with pytest.raises(ValueError):
+        K.conv_pack_table([], "cpu")
+    assert [K.pack_blocks(*a) for a in [(64, 64, 3, 3), (768, 64, 1, 1), (64, 2, 7, 7), (128, 128, 4, 4)]] == \
+        [10, 12, 64, 64]
+    tab, nblocks = K.conv_pack_table([[0, 0, 64, 64, 3, 3, 0, 0], [0, 0, 768, 64, 1, 1, 0, 0]], "cpu")
+    assert nblocks == 22 and tab.tolist()[16:19] == [0, 10, 22]
+
+
 def test_tflash_dq_dispatch():
     """the temporal attention core backward (cesm_tflash_bwd_variant, host only): the one-pass fused kernel for every
     F >= 8 (round 5), the two-kernel form (block-per-pixel dq kernel + the dk / dv kernel) below"""
