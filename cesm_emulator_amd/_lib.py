@@ -14,7 +14,8 @@ PKG = Path(__file__).resolve().parent
 HEADER = PKG.parent / "include" / "cesm_hip.h"
 import os
 
-# CESM_HIP_LIB selects a diagnostic build (tools/build_diag.sh); default: the in-tree product library
+# CESM_HIP_LIB selects a variant library (python -m cesm_emulator_amd.build --variant NAME); default: the in-tree
+# product library
 LIBPATH = Path(os.environ["CESM_HIP_LIB"]) if os.environ.get("CESM_HIP_LIB") else PKG / "libcesm_hip.so"
 
 def header_abi_version(path: Path = HEADER) -> int:

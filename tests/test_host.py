@@ -28,6 +28,33 @@ def test_library_exports_every_header_symbol():
     _lib.lib()  # argtypes bind cleanly
 
 
+def test_build_commands():
+    """The compile commands of the product and of a variant library (nothing is compiled): the set of sources and the
+    per-source flag table are pinned here as literals, and a variant differs from the product only by what it was
+    asked to differ in."""
+    from cesm_emulator_amd import build as B
+    srcs = B.sources()
+    assert [s.name for s in srcs] == ["attn.hip", "conv.hip", "gn.hip", "misc.hip", "norm.hip", "qkvbwd.hip",
+                                      "sla_fused.hip", "tblock.hip", "tflash.hip"]
+    no_slp = {"tblock.hip", "tflash.hip", "attn.hip"}
+    no_nans = no_slp | {"sla_fused.hip"}
+
+    def expect(s, obj_dir, special, extra=()):
+        return [B.HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", os.path.join(ROOT, "include"),
+                *special, *extra, "-c", os.path.join(ROOT, "cesm_emulator_amd", "csrc", s.name), "-o",
+                os.path.join(ROOT, "build", obj_dir, s.stem + ".o")]
+
+    extra = ["-DCESM_TW_STAMPS", "-DCESM_H3_STAMPS"]
+    assert str(B.variant_dir("ab")) == os.path.join(ROOT, "build", "var_ab")
+    assert str(B.variant_lib("ab")) == os.path.join(ROOT, "cesm_emulator_amd", "libcesm_hip_ab.so")
+    for s in srcs:
+        special = ["-fno-slp-vectorize"] * (s.name in no_slp) + ["-fno-honor-nans"] * (s.name in no_nans)
+        assert not (s.name.startswith("conv") and special)
+        assert B.compile_cmd(s) == expect(s, "obj", special), s.name
+        assert B.compile_cmd(s, B.variant_dir("ab"), extra) == expect(s, "var_ab", special, extra), s.name
+        assert B.compile_cmd(s, B.variant_dir("ab"), per_source=False) == expect(s, "var_ab", []), s.name
+
+
 def test_kernels_refuse_cpu_tensors():
     from cesm_emulator_amd import kernels as K
     with pytest.raises(RuntimeError):

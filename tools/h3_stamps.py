@@ -1,8 +1,8 @@
 """Phase timeline of the halo conv (conv3x3_bf16_kernel<36,7>) from the diagnostic build's in-kernel stamps
-(-DCESM_H3_STAMPS, tools/build_diag.sh): per wave, cycles in [end-of-chunk barrier, stage issue, landing wait,
+(-DCESM_H3_STAMPS, a build.py variant): per wave, cycles in [end-of-chunk barrier, stage issue, landing wait,
 post-landing barrier, MFMA taps, epilogue], and whether the two blocks sharing a CU run their chunks in phase.
 
-usage: DIAG_FLAGS=-DCESM_H3_STAMPS bash tools/build_diag.sh   (in the container)
+usage: python -m cesm_emulator_amd.build --variant diag --flags="-DCESM_TW_STAMPS -DCESM_H3_STAMPS"
        CESM_HIP_LIB=cesm_emulator_amd/libcesm_hip_diag.so python tools/h3_stamps.py [levels]"""
 import ctypes
 import os
