@@ -148,7 +148,7 @@ def _gflat(p):
 
 # ============================================================================ conv helpers
 class ConvSpec:
-    """Geometry of one conv-like layer in GEMM terms (see csrc/conv.hip)."""
+    """Geometry of one conv-like layer in GEMM terms (see csrc/conv_common.h)."""
 
     def __init__(self, mod):
         w = mod.weight

@@ -46,7 +46,7 @@ int cesm_abi_version(void);
  * distributed.XgmiModelReducer). */
 int cesm_hold_cus(int nblk, float usec, hipStream_t stream);
 
-/* ---- convolutions (csrc/conv.hip) -------------------------------------------------------
+/* ---- convolutions (csrc/conv.hip, conv_wgrad.hip) -------------------------------------
  * Generic implicit-GEMM conv on MFMA. Replaces nn.Conv3d (1,k,k) at video_net.py:215 (Block.proj),
  * :246 (res_conv), :61-62 (Downsample), nn.ConvTranspose3d at :65-66 (Upsample), the attention
  * projections nn.Linear :380-381 and 1x1 nn.Conv2d :322-323, and all their data gradients.

@@ -34,8 +34,8 @@ def test_build_commands():
     asked to differ in."""
     from cesm_emulator_amd import build as B
     srcs = B.sources()
-    assert [s.name for s in srcs] == ["attn.hip", "conv.hip", "gn.hip", "misc.hip", "norm.hip", "qkvbwd.hip",
-                                      "sla_fused.hip", "tblock.hip", "tflash.hip"]
+    assert [s.name for s in srcs] == ["attn.hip", "conv.hip", "conv_wgrad.hip", "gn.hip", "misc.hip", "norm.hip",
+                                      "qkvbwd.hip", "sla_fused.hip", "tblock.hip", "tflash.hip"]
     no_slp = {"tblock.hip", "tflash.hip", "attn.hip"}
     no_nans = no_slp | {"sla_fused.hip"}
 
