@@ -7,6 +7,7 @@
 //  * dtype casts and the training-window gather (dataset_single_member.py:168-196)
 #include "common.h"
 #include "cesm_hip.h"
+#include "stem_dgrad.h"  // the stem's data gradient: kernels and launcher (cesm_stem_dgrad below)
 
 namespace {
 
@@ -409,6 +410,12 @@ int cesm_cast(int dtype_in, int dtype_out, const void* x, void* y, int64_t n, hi
   else
     return CESM_EINVAL;
   return cesm_launch_status();
+}
+
+// stem data gradient (input gradients; kernels: stem_dgrad.h)
+int cesm_stem_dgrad(int dtype, const void* dy, const float* w, float* dxt, float* dcond, int B, int F, int Fx, int Fc,
+                    int H, int W, int Co, int KS, hipStream_t stream) {
+  return stem_dgrad_launch(dtype, dy, w, dxt, dcond, B, F, Fx, Fc, H, W, Co, KS, stream);
 }
 
 int cesm_window_gather(const float* cond, const float* tgt, const int64_t* items, float* cwin, float* x0,

@@ -11,7 +11,7 @@ import os
 
 import torch
 
-from ._lib import call, lib
+from ._lib import KernelError, call, lib
 
 F32, BF16 = 0, 1
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
@@ -258,6 +258,24 @@ def stem_wgrad(xt, cond, dy, dw, F, accumulate=True):
     part = empty((nblk, Co * 2 * KS * KS), torch.float32, xt.device)
     call("cesm_stem_wgrad", dtcode(dy), P(xt), P(cond), P(dy), P(dw), P(part), nblk, B, F, Fx, Fc, H, W, Co, KS,
          int(accumulate), S())
+
+
+def stem_dgrad(dy, w, B, F, Fx, Fc, want_xt=True, want_cond=True):
+    """data gradient of the stem (csrc/stem_dgrad.h): dy [B*F, H, W, Co] (the tensor stem_wgrad reads), w the fp32
+    stem weight [Co, 2, 1, KS, KS].  Returns (dxt [B, Fx, H, W], dcond [B, Fc, H, W]) fp32, None where not wanted; an
+    input that was broadcast over frames (Fx or Fc == 1 < F) gets the sum over the F frames."""
+    Nb, H, W, Co = dy.shape
+    KS = w.shape[-1]
+    _chk(dy, (B * F, H, W, Co))
+    _chk(w, (Co, 2, 1, KS, KS), torch.float32)
+    dxt = empty((B, Fx, H, W), torch.float32, dy.device) if want_xt else None
+    dcond = empty((B, Fc, H, W), torch.float32, dy.device) if want_cond else None
+    rc = lib().cesm_stem_dgrad(dtcode(dy), P(dy), P(w), P(dxt), P(dcond), B, F, Fx, Fc, H, W, Co, KS, S())
+    if rc == -2:  # CESM_EUNSUPPORTED
+        raise ValueError(f"stem_dgrad: unsupported shape KS={KS} Co={Co} F={F} Fx={Fx} Fc={Fc}")
+    if rc != 0:
+        raise KernelError(f"cesm_stem_dgrad failed with code {rc}")
+    return dxt, dcond
 
 
 def head_fwd(x, w, b, B, F):

@@ -125,9 +125,30 @@ class RunCtx:
         self._mark = None
 
 
+# Scoped switches of the input-gradient path.  _PARAM_GRADS_OFF: set by backward_from for its own duration when the
+# backward is to produce no parameter gradient; gbuf then yields None for every parameter, so no p.grad is created or
+# touched (every kernel the backward launches takes null gradient destinations: DESIGN "Input gradients").
+# _INPUTS_ONLY: set by input_grads_only() around a caller's backward.
+_PARAM_GRADS_OFF = [False]
+_INPUTS_ONLY = [False]
+
+
+class input_grads_only:
+    """Context: backwards of the HIP network started inside it compute the gradients of x_t / cond only -- no
+    parameter gradient is computed, no p.grad is created or changed and the data-parallel readiness hook is not fired
+    (saliency.input_grads)."""
+
+    def __enter__(self):
+        self._prev, _INPUTS_ONLY[0] = _INPUTS_ONLY[0], True
+
+    def __exit__(self, *exc):
+        _INPUTS_ONLY[0] = self._prev
+        return False
+
+
 def gbuf(p):
     """fp32 gradient destination for parameter p (kernels accumulate into it)."""
-    if p is None or not p.requires_grad:
+    if p is None or _PARAM_GRADS_OFF[0] or not p.requires_grad:
         return None
     if p.grad is None:
         p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
@@ -792,14 +813,23 @@ class UNetModel3D(nn.Module):
         tape.head_in = x
         return (out, tape) if save else out
 
-    def backward_from(self, dout, tape):
+    def backward_from(self, dout, tape, want_xt=False, want_cond=False, param_grads=True):
         """backward of the forward that recorded `tape` (held by that forward's autograd node, so several
-        grad-enabled forwards may be in flight and each backward replays its own activations)."""
+        grad-enabled forwards may be in flight and each backward replays its own activations).  Returns (dxt, dcond):
+        the gradients of the forward's x_t [B,Fx,H,W] / cond [B,Fc,H,W] where asked for, else None.
+        param_grads=False: no parameter gradient is computed (no p.grad created or changed, no readiness hook)."""
         if tape is None:
             raise RuntimeError("backward called twice for one forward (its tape was already consumed)")
+        prev, _PARAM_GRADS_OFF[0] = _PARAM_GRADS_OFF[0], not param_grads
+        try:
+            return self._backward_from(dout, tape, want_xt, want_cond, param_grads)
+        finally:
+            _PARAM_GRADS_OFF[0] = prev
+
+    def _backward_from(self, dout, tape, want_xt, want_cond, param_grads):
         rc = tape.rc
         dev = dout.device
-        hook = getattr(self, "_grad_ready", None)
+        hook = getattr(self, "_grad_ready", None) if param_grads else None
 
         def done(*mods):  # data-parallel overlap: these modules' gradients are final (distributed.arm)
             if hook is not None:
@@ -854,12 +884,17 @@ class UNetModel3D(nn.Module):
                 K.stem_wgrad(tape.x_t, tape.cond, dx, wi, rc.F)
             if bi is not None:
                 K.colsum(dx, bi)
+        dxt = dcond = None
+        if want_xt or want_cond:  # input gradients: the stem's data gradient, on the main stream
+            dxt, dcond = K.stem_dgrad(dx, self.input_conv.weight, rc.B, rc.F, tape.x_t.shape[1], tape.cond.shape[1],
+                                      want_xt, want_cond)
         # time MLP: temb = Lin3(SiLU(Lin1(emb)))
         l1, l3 = self.time_mlp[1], self.time_mlp[3]
         dh1 = torch.empty_like(tape.h1)
         K.linear_small_bwd(tape.h1, l3.weight, rc.dt, dh1, gbuf(l3.weight), gbuf(l3.bias), True, False)
         K.linear_small_bwd(tape.emb, l1.weight, dh1, None, gbuf(l1.weight), gbuf(l1.bias), False, False)
         rc.join()
+        return dxt, dcond
 
 
 class _NetFunction(torch.autograd.Function):
@@ -871,14 +906,19 @@ class _NetFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        if torch.is_grad_enabled():  # the engine runs a backward in grad mode only under create_graph=True
+            raise RuntimeError("cesm_emulator_amd: the HIP network is differentiable once; a double backward "
+                               "(create_graph=True) through it is not supported")
         tape, ctx.tape = ctx.tape, None  # activations freed as soon as the backward has run
-        ctx.net.backward_from(dout, tape)
-        return None, None, None, None, None
+        _, want_xt, want_cond, _, _ = ctx.needs_input_grad
+        dxt, dcond = ctx.net.backward_from(dout, tape, want_xt, want_cond, param_grads=not _INPUTS_ONLY[0])
+        return None, dxt, dcond, None, None
 
 
 def net_apply(net, x_t, cond, t):
-    """Run the HIP network; records the backward tape when a gradient is needed."""
+    """Run the HIP network; records the backward tape when a gradient is needed: of the parameters (the stem weight
+    stands for them) or of the inputs x_t / cond (`_NetFunction` sees which through ctx.needs_input_grad)."""
     anchor = net.input_conv.weight
-    if torch.is_grad_enabled() and anchor.requires_grad:
+    if torch.is_grad_enabled() and (anchor.requires_grad or x_t.requires_grad or cond.requires_grad):
         return _NetFunction.apply(net, x_t, cond, t, anchor)
     return net.run_forward(x_t, cond, t, save=False)

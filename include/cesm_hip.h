@@ -119,6 +119,14 @@ int cesm_stem_fwd(int dtype, const float* xt, const float* cond, const float* w,
                   int F, int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream);
 int cesm_stem_wgrad(int dtype, const float* xt, const float* cond, const void* dy, float* dw, float* part, int nblk,
                     int B, int F, int Fx, int Fc, int H, int W, int Co, int KS, int accumulate, hipStream_t stream);
+/* Data gradient of the stem (input gradients: d/d x_t and d/d cond).  dy [B*F][H][W][Co] in the compute dtype (the
+ * tensor cesm_stem_wgrad reads), w the fp32 master weight [Co][2][KS][KS]; dxt [B][Fx][H][W] and dcond [B][Fc][H][W]
+ * fp32 are overwritten, each nullable (then not written; its sum rides in the same MFMA rows).  An input the forward broadcast over frames
+ * (Fx or Fc == 1 with F > 1) receives the sum over all F frames.  Deterministic (no atomics).  CESM_EUNSUPPORTED
+ * unless KS is odd and <= 7, Co % 64 == 0 and Fx, Fc are 1 or F.  (Added without a CESM_ABI_VERSION bump: no existing
+ * argument list changed.) */
+int cesm_stem_dgrad(int dtype, const void* dy, const float* w, float* dxt, float* dcond,
+                    int B, int F, int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream);
 /* head Conv3d(C->1,1) (video_net.py:763) evaluated on frame F//2 only (model.py:124-130). */
 int cesm_head_fwd(int dtype, const void* x, const float* w, const float* bias, float* out, int B, int F, int HW, int C,
                   hipStream_t stream);
