@@ -135,6 +135,60 @@ __global__ void ddpm_step_kernel(const float* __restrict__ x, const float* __res
   }
 }
 
+// Generalized DDIM step (Song et al. 2021, eq. 12) from t to t_prev < t, per sample (Diffusion.ddim_coefs is the
+// same arithmetic on the host):
+//   x_prev = a x_t + b eps + sigma z,  with ac = alphas_cumprod[t], ap = t_prev < 0 ? 1 : alphas_cumprod[t_prev],
+//   sigma = eta sqrt((1-ap)/(1-ac)) sqrt(1 - ac/ap),  a = sqrt(ap/ac),
+//   b = sqrt(max(1 - ap - sigma^2, 0)) - sqrt(ap (1-ac)/ac)
+// a, b, sigma formed in double from the two fp32 table values and rounded to fp32 once each; the update itself is
+// fp32.  eta = 0 is the deterministic DDIM, eta = 1 with t_prev = t - 1 the DDPM step (there 1 - ap - sigma^2 is
+// exactly 0 on the last step and may round below it, hence the max).  blockIdx.y = sample, so the coefficients cost
+// every thread two table reads; VEC: HW % 4 == 0 and every pointer 16-byte aligned -> 16-byte accesses (no tail is
+// left then), else one element per access.  z == nullptr: no noise term, z is not read.  out may alias x (each thread
+// reads its elements before it writes them), so neither carries __restrict__.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const float* __restrict__ eps,
+                                                        const float* __restrict__ z, const int64_t* __restrict__ t,
+                                                        const int64_t* __restrict__ tprev,
+                                                        const float* __restrict__ acp, float eta, float* out,
+                                                        int64_t HW) {
+  const int b = blockIdx.y;
+  const int64_t tp = tprev[b];
+  const double ac = (double)acp[t[b]];
+  const double ap = tp < 0 ? 1.0 : (double)acp[tp];
+  const double sg = (double)eta * sqrt((1.0 - ap) / (1.0 - ac)) * sqrt(1.0 - ac / ap);
+  const float ca = (float)sqrt(ap / ac);
+  const float cb = (float)(sqrt(fmax(1.0 - ap - sg * sg, 0.0)) - sqrt(ap * (1.0 - ac) / ac));
+  const float cs = (float)sg;
+  const int64_t base = (int64_t)b * HW;
+  x += base, eps += base, out += base;
+  if (z) z += base;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (VEC) {
+    const int64_t nv = HW >> 2;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < nv; e += stride) {
+      float xv[4], ev[4], m[4];
+      load4(x + e * 4, xv);
+      load4(eps + e * 4, ev);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) m[i] = ca * xv[i] + cb * ev[i];
+      if (z) {
+        float zv[4];
+        load4(z + e * 4, zv);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) m[i] += cs * zv[i];
+      }
+      store4(out + e * 4, m);
+    }
+  } else {
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < HW; e += stride) {
+      float m = ca * x[e] + cb * eps[e];
+      if (z) m += cs * z[e];
+      out[e] = m;
+    }
+  }
+}
+
 // loss partials: part[blk] = sum (pred - noise)^2
 __global__ void mse_partial_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                    float* __restrict__ part, int64_t n) {
@@ -351,6 +405,21 @@ int cesm_ddpm_step(const float* x, const float* eps, const float* z, const int64
   const unsigned grid = (unsigned)std::min<int64_t>(cdiv((int64_t)B * HW, 256), 4096);
   ddpm_step_kernel<<<grid, 256, 0, stream>>>(x, eps, z, t, sqrt_recip_alphas, betas, sqrt_one_minus_ac,
                                              posterior_variance, out, B, HW);
+  return cesm_launch_status();
+}
+
+int cesm_ddim_step(const float* x, const float* eps, const float* z, const int64_t* t, const int64_t* t_prev,
+                   const float* alphas_cumprod, float eta, float* out, int B, int64_t HW, int T, hipStream_t stream) {
+  if (B < 1 || B > 65535 || HW < 1 || T < 1 || !(eta >= 0.f)) return CESM_EINVAL;
+  if (eta == 0.f) z = nullptr;
+  const bool vec = HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)eps | (uintptr_t)z | (uintptr_t)out) & 15) == 0;
+  // about 4096 blocks over the batch: grid-stride inside a sample
+  const int64_t per = std::max<int64_t>(1, 4096 / B);
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv(vec ? HW / 4 : HW, 256), per), (unsigned)B);
+  if (vec)
+    ddim_step_kernel<true><<<grid, 256, 0, stream>>>(x, eps, z, t, t_prev, alphas_cumprod, eta, out, HW);
+  else
+    ddim_step_kernel<false><<<grid, 256, 0, stream>>>(x, eps, z, t, t_prev, alphas_cumprod, eta, out, HW);
   return cesm_launch_status();
 }
 

@@ -723,6 +723,32 @@ def ddpm_step(x, eps, z, t, sra, betas, s1a, pv, out=None):
     return out
 
 
+def ddim_step(x, eps, z, t, t_prev, alphas_cumprod, eta, out=None):
+    """Fused generalized DDIM update (cesm_ddim_step; coefficients: Diffusion.ddim_coefs): t, t_prev [B] int64 device
+    tensors with t_prev < t < T (the caller's range check, the kernel has none); z=None or eta=0 drops the noise term;
+    out may be x."""
+    B = x.shape[0]
+    _chk(x, dtype=torch.float32)
+    _chk(eps, x.shape, torch.float32)
+    if z is not None:
+        _chk(z, x.shape, torch.float32)
+    _chk(t, (B,), torch.int64)
+    _chk(t_prev, (B,), torch.int64)
+    _chk(alphas_cumprod, dtype=torch.float32)
+    if alphas_cumprod.ndim != 1:
+        raise RuntimeError("alphas_cumprod must be 1-D")
+    eta = float(eta)
+    if not eta >= 0.0:
+        raise ValueError(f"eta must be >= 0, got {eta}")
+    if out is None:
+        out = empty(x.shape, torch.float32, x.device)
+    else:
+        _chk(out, x.shape, torch.float32)
+    call("cesm_ddim_step", P(x), P(eps), P(z), P(t), P(t_prev), P(alphas_cumprod), eta, P(out), B, x.numel() // B,
+         alphas_cumprod.numel(), S())
+    return out
+
+
 def mse(pred, tgt):
     loss = empty((), torch.float32, pred.device)
     part = empty((512,), torch.float32, pred.device)

@@ -154,23 +154,137 @@ class Diffusion(nn.Module):
                 noise = torch.randn_like(x_t)
             return K.ddpm_step(x_t, eps, noise.float().contiguous(), t, *self._coefs())
 
+    def sample_schedule(self, steps):
+        """The `steps` time indices tau of a strided sampling run: an increasing sub-sequence of 0 … T-1 that ends at
+        T-1 and (for steps >= 2) starts at 0, tau_i = round(i (T-1) / (steps-1)) in exact integer arithmetic (halves
+        round up).  Sampling walks it from the back; the t_prev of tau_0 is -1."""
+        steps, T = int(steps), self.T
+        if not 1 <= steps <= T:
+            raise ValueError(f"steps must be in 1 … T = {T}, got {steps}")
+        if steps == 1:
+            return [T - 1]
+        return [(2 * i * (T - 1) + (steps - 1)) // (2 * (steps - 1)) for i in range(steps)]
+
+    def _ddim_args(self, t, t_prev, eta):
+        """t, t_prev as broadcast int64 tensors on the schedule's device and eta as a float, range-checked (the update
+        kernel checks nothing): -1 <= t_prev < t < T, eta >= 0"""
+        dev = self.alphas_cumprod.device
+        t = torch.as_tensor(t, device=dev).long()
+        t_prev = torch.as_tensor(t_prev, device=dev).long()
+        t, t_prev = torch.broadcast_tensors(t, t_prev)
+        eta = float(eta)
+        if not eta >= 0.0:
+            raise ValueError(f"eta must be >= 0, got {eta}")
+        if bool(((t < 0) | (t >= self.T) | (t_prev < -1) | (t_prev >= t)).any()):
+            raise ValueError(f"DDIM step needs -1 <= t_prev < t < T = {self.T}, got t = {t.tolist()}, "
+                             f"t_prev = {t_prev.tolist()}")
+        return t.contiguous(), t_prev.contiguous(), eta
+
+    def ddim_coefs(self, t, t_prev, eta=0.0):
+        """(a, b, sigma) of the generalized DDIM step x_prev = a x_t + b eps + sigma z (Song et al. 2021, eq. 12) from
+        t to t_prev < t, as float64 tensors of t's shape; t, t_prev: ints or integer tensors, t_prev = -1 means
+        alphas_cumprod_prev = 1 (the step returns the x0 estimate).  Computed in float64 from the fp32 alphas_cumprod
+        entries; the update kernel (csrc/misc.hip ddim_step_kernel) does the same arithmetic and rounds each of the
+        three to fp32 once.  eta = 0: deterministic DDIM; eta = 1 with t_prev = t - 1: the DDPM step."""
+        t, t_prev, eta = self._ddim_args(t, t_prev, eta)
+        ac = self.alphas_cumprod
+        at = ac[t].double()
+        ap = torch.where(t_prev < 0, torch.ones_like(at), ac[t_prev.clamp_min(0)].double())
+        sigma = eta * torch.sqrt((1.0 - ap) / (1.0 - at)) * torch.sqrt(1.0 - at / ap)
+        a = torch.sqrt(ap / at)
+        b = torch.sqrt((1.0 - ap - sigma * sigma).clamp_min(0.0)) - torch.sqrt(ap * (1.0 - at) / at)
+        return a, b, sigma
+
     @torch.no_grad()
-    def sample(self, cond, shape, device, use_graph=None, x_T=None, noise_seq=None):
+    def ddim_step(self, x_t, cond, t, t_prev, eta=0.0, noise=None):
+        """One generalized DDIM step t -> t_prev (per sample; ddim_coefs has the formula): model evaluation + one
+        fused update kernel, the few-step counterpart of p_sample.  Step noise is used (and, without `noise`, drawn
+        with randn_like) only when eta > 0 and some t_prev >= 0."""
+        with torch.inference_mode():
+            x_t = x_t.float().contiguous()
+            B = x_t.shape[0]
+            t, t_prev, eta = self._ddim_args(t, t_prev, eta)
+            t = t.to(x_t.device).expand(B).contiguous()
+            t_prev = t_prev.to(x_t.device).expand(B).contiguous()
+            eps = self.model(x_t, cond, t).float().contiguous()
+            z = None
+            if eta > 0.0 and bool((t_prev >= 0).any()):
+                z = (torch.randn_like(x_t) if noise is None else noise.to(x_t.device)).float().contiguous()
+            return K.ddim_step(x_t, eps, z, t, t_prev, self.alphas_cumprod, eta)
+
+    @torch.no_grad()
+    def sample(self, cond, shape, device, use_graph=None, x_T=None, noise_seq=None, steps=None, ddim_eta=0.0):
         """model.py:186-194.  On the GPU every p_sample step is ONE replay of a captured HIP graph (the
         F=1 network forward + the fused update); the host only sets t and draws the step noise.  RNG use
         is the reference's: randn(shape) for x_T, then randn_like(x) for every step with t > 0, drawn
         outside the graph on the default generator, so the result equals the eager loop.  Test hooks:
         x_T (initial state) and noise_seq ([T, *shape], noise of step i = noise_seq[i], i = 0 for t = T-1)
-        replace the draws.  use_graph=False (or CESM_SAMPLE_GRAPH=0) runs the eager loop."""
+        replace the draws.  use_graph=False (or CESM_SAMPLE_GRAPH=0) runs the eager loop.
+
+        steps=N (1 <= N <= T) samples in N generalized DDIM steps over sample_schedule(N) instead (ddim_eta = 0:
+        deterministic; > 0: stochastic, 1 on the full grid is DDPM); steps=None is the ancestral loop above whatever
+        ddim_eta is.  RNG use then: randn(shape) for x_T unless given, and only for ddim_eta > 0 one randn_like per
+        executed step except the last, in step order, outside the graph on the default generator; noise_seq is
+        [N, *shape] (entry k for executed step k, the last one unused).  ddim_eta = 0 with x_T draws nothing."""
+        return self._sample(cond, shape, device, use_graph, x_T, noise_seq, steps, ddim_eta, False)
+
+    def _sample(self, cond, shape, device, use_graph, x_T, noise_seq, steps, ddim_eta, paired):
+        """sample(); paired: the batch is two halves that get the same x_T and the same step noise (drawn for one
+        half, copied to the other: counterfactual_delta)"""
+        if steps is not None:
+            tau = self.sample_schedule(steps)
+            ddim_eta = float(ddim_eta)
+            if not ddim_eta >= 0.0:
+                raise ValueError(f"ddim_eta must be >= 0, got {ddim_eta}")
+        if paired and shape[0] % 2:
+            raise ValueError("paired sampling needs an even batch")
+
+        def randn():
+            if not paired:
+                return torch.randn(shape, device=device)
+            return torch.randn((shape[0] // 2, *shape[1:]), device=device).repeat(2, *([1] * (len(shape) - 1)))
+
+        def fill(z):
+            if paired:
+                h = z.shape[0] // 2
+                z[:h].normal_()
+                z[h:].copy_(z[:h])
+            else:
+                z.normal_()
+
         with torch.inference_mode():
             B = shape[0]
-            x = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float().clone()
+            x = randn() if x_T is None else x_T.to(device).float().clone()
             if use_graph is None:
                 use_graph = os.environ.get("CESM_SAMPLE_GRAPH", "1") != "0"
+            if steps is not None:
+                # executed step k: t = tau[-1-k] -> t_prev = tau[-2-k], -1 after tau[0]
+                pairs = list(zip(reversed(tau), reversed([-1] + tau[:-1])))
+                noisy = ddim_eta > 0.0
+                if not use_graph:
+                    for k, (tt, tp) in enumerate(pairs):
+                        t_tensor = torch.full((B,), tt, device=device, dtype=torch.long)
+                        tp_tensor = torch.full((B,), tp, device=device, dtype=torch.long)
+                        nz = None
+                        if noisy and tp >= 0:
+                            nz = noise_seq[k].to(device) if noise_seq is not None else randn()
+                        x = self.ddim_step(x, cond, t_tensor, tp_tensor, ddim_eta, noise=nz)
+                    return x
+                step = GraphSampleStep(self, cond, x, ddim_eta=ddim_eta)
+                for k, (tt, tp) in enumerate(pairs):
+                    if noisy and tp >= 0:  # the last step's sigma is exactly 0: z stays as it is
+                        if noise_seq is not None:
+                            step.z.copy_(noise_seq[k])
+                        else:
+                            fill(step.z)
+                    step.run(tt, tp)
+                return step.x
             if not use_graph:
                 for i, tt in enumerate(reversed(range(self.T))):
                     t_tensor = torch.full((B,), tt, device=device, dtype=torch.long)
                     nz = None if noise_seq is None or tt == 0 else noise_seq[i].to(device)
+                    if paired and nz is None and tt != 0:
+                        nz = randn()
                     x = self.p_sample(x, cond, t_tensor, noise=nz)
                 return x
             step = GraphSampleStep(self, cond, x)
@@ -180,7 +294,7 @@ class Diffusion(nn.Module):
                 elif noise_seq is not None:
                     step.z.copy_(noise_seq[i])
                 else:
-                    step.z.normal_()
+                    fill(step.z)
                 step.run(tt)
             return step.x
 
@@ -189,14 +303,22 @@ class GraphSampleStep:
     """One DDPM sampling step (model eval + fused update, in place on a static x) captured as a HIP graph
     (torch.cuda.graph drives hipStreamBeginCapture; every kernel launches on the capturing stream).
     Static inputs: x [B,1,H,W] fp32 (updated in place), cond, t [B] int64, z (step noise; zero at t=0,
-    where posterior_variance[0] = 0 makes the noise term vanish as in the reference's t=0 branch)."""
+    where posterior_variance[0] = 0 makes the noise term vanish as in the reference's t=0 branch).
 
-    def __init__(self, diffusion, cond, x):
+    ddim_eta=None is that DDPM step.  With ddim_eta >= 0 the captured update is the generalized DDIM step instead
+    (Diffusion.ddim_step): t_prev [B] int64 is a further static input, run(tt, tt_prev) sets both, and z exists only
+    for ddim_eta > 0 (None at 0: the graph holds no noise buffer)."""
+
+    def __init__(self, diffusion, cond, x, ddim_eta=None):
         self.d = diffusion
+        self.eta = None if ddim_eta is None else float(ddim_eta)
+        if self.eta is not None and not self.eta >= 0.0:
+            raise ValueError(f"ddim_eta must be >= 0, got {ddim_eta}")
         self.x = x.float().contiguous()
         self.cond = cond.float().contiguous()
         self.t = torch.zeros(x.shape[0], dtype=torch.long, device=x.device)
-        self.z = torch.zeros_like(self.x)
+        self.t_prev = None if self.eta is None else torch.full_like(self.t, -1)
+        self.z = torch.zeros_like(self.x) if self.eta is None or self.eta > 0.0 else None
         x0 = self.x.clone()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -211,8 +333,18 @@ class GraphSampleStep:
 
     def _step(self):
         eps = self.d.model(self.x, self.cond, self.t).float().contiguous()
-        K.ddpm_step(self.x, eps, self.z, self.t, *self.d._coefs(), out=self.x)
+        if self.eta is None:
+            K.ddpm_step(self.x, eps, self.z, self.t, *self.d._coefs(), out=self.x)
+        else:
+            K.ddim_step(self.x, eps, self.z, self.t, self.t_prev, self.d.alphas_cumprod, self.eta, out=self.x)
 
-    def run(self, tt):
+    def run(self, tt, tt_prev=None):
+        """one step at time index tt for every sample; a DDIM step also needs its target tt_prev (-1 <= tt_prev < tt)"""
+        if (tt_prev is None) != (self.t_prev is None):
+            raise ValueError("run(tt) is the DDPM step, run(tt, tt_prev) the DDIM step (ddim_eta given)")
+        if not 0 <= tt < self.d.T or (tt_prev is not None and not -1 <= tt_prev < tt):
+            raise ValueError(f"step indices out of range: t = {tt}, t_prev = {tt_prev}, T = {self.d.T}")
         self.t.fill_(tt)
+        if tt_prev is not None:
+            self.t_prev.fill_(tt_prev)
         self.graph.replay()

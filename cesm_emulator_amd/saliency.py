@@ -33,6 +33,26 @@ def input_grads(diffusion, x0, cond, t=None, noise=None):
     return loss.detach(), dxt, dcond
 
 
+def counterfactual_delta(diffusion, cond, scale_mask=None, scale=1.1, steps=None, ddim_eta=0.0, paired=False):
+    """Sampled response to scaled emissions (the reference's train.py counterfactual_delta): sample(cond2) -
+    sample(cond) with cond2 = cond * scale, or cond * (1 + (scale - 1) * scale_mask) where a mask is given.  steps and
+    ddim_eta go to Diffusion.sample (steps=None: the full ancestral loop).
+
+    Default: two sampling runs, base first, each drawing its own x_T and step noise (the reference's semantics), so
+    the difference also carries the sampling noise.  paired=True: ONE run of batch 2B over [cond, cond2] in which both
+    halves get the same x_T and the same step noise (drawn for B samples, copied to the other half); the difference
+    then isolates the change in cond."""
+    cond2 = cond * scale if scale_mask is None else cond * (1.0 + (scale - 1.0) * scale_mask)
+    B, H, W = cond.shape[0], cond.shape[-2], cond.shape[-1]
+    if paired:
+        x = diffusion._sample(torch.cat([cond, cond2], dim=0), (2 * B, 1, H, W), cond.device, None, None, None, steps,
+                              ddim_eta, True)
+        return x[B:] - x[:B]
+    base = diffusion.sample(cond, (B, 1, H, W), cond.device, steps=steps, ddim_eta=ddim_eta)
+    pert = diffusion.sample(cond2, (B, 1, H, W), cond.device, steps=steps, ddim_eta=ddim_eta)
+    return pert - base
+
+
 def saliency_wrt_cond(diffusion, x0, cond, t=None, noise=None, normalize=True):
     """|d loss / d cond| in cond's shape (the reference's train.py saliency_wrt_cond); with normalize, every sample's
     map(s) divided by its spatial maximum + 1e-8."""

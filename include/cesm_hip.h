@@ -309,6 +309,15 @@ int cesm_q_sample(const float* x0, const float* noise, const int64_t* t, const f
 int cesm_ddpm_step(const float* x, const float* eps, const float* z, const int64_t* t, const float* sqrt_recip_alphas,
                    const float* betas, const float* sqrt_one_minus_ac, const float* posterior_variance, float* out,
                    int B, int64_t HW, hipStream_t stream);
+/* Diffusion.ddim_step update (generalized DDIM step of Song et al. 2021, eq. 12; few-step sampling), fused:
+ * out = a x + b eps + sigma z, with (a, b, sigma) formed per sample on the device, in double, from
+ * alphas_cumprod[t] and alphas_cumprod[t_prev] (t_prev < 0: 1, the step returns the x0 estimate) -- the arithmetic of
+ * Diffusion.ddim_coefs.  t, t_prev: [B] device tensors, t_prev[b] < t[b] < T (checked by the caller, not here), t may
+ * differ across the batch; eta >= 0 (0: deterministic; 1 with t_prev = t - 1: the DDPM step).  z == NULL or eta == 0:
+ * no noise term, z is not read.  out may alias x.  x, eps, z, out: [B][HW] fp32; alphas_cumprod: [T] fp32.
+ * An added entry point (no existing argument list changed): the ABI version stays, as for cesm_stem_dgrad. */
+int cesm_ddim_step(const float* x, const float* eps, const float* z, const int64_t* t, const int64_t* t_prev,
+                   const float* alphas_cumprod, float eta, float* out, int B, int64_t HW, int T, hipStream_t stream);
 int cesm_mse(const float* pred, const float* tgt, float* loss, float* part, int64_t n, hipStream_t stream);
 int cesm_mse_bwd(const float* pred, const float* tgt, const float* gscale, float* dpred, int64_t n,
                  hipStream_t stream);
