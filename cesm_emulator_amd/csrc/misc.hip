@@ -8,6 +8,7 @@
 #include "common.h"
 #include "cesm_hip.h"
 #include "stem_dgrad.h"  // the stem's data gradient: kernels and launcher (cesm_stem_dgrad below)
+#include "multivar.h"    // stem and head for 2..4 target variables: kernels and launchers (cesm_*_mv below)
 
 namespace {
 
@@ -485,6 +486,29 @@ int cesm_cast(int dtype_in, int dtype_out, const void* x, void* y, int64_t n, hi
 int cesm_stem_dgrad(int dtype, const void* dy, const float* w, float* dxt, float* dcond, int B, int F, int Fx, int Fc,
                     int H, int W, int Co, int KS, hipStream_t stream) {
   return stem_dgrad_launch(dtype, dy, w, dxt, dcond, B, F, Fx, Fc, H, W, Co, KS, stream);
+}
+
+// stem and head for V target variables (kernels and launchers: multivar.h; V == 1 runs the entry points above)
+int cesm_stem_fwd_mv(int dtype, const float* xt, const float* cond, const float* w, const float* bias, void* y, int B,
+                     int V, int F, int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream) {
+  return mv_stem_fwd_launch(dtype, xt, cond, w, bias, y, B, V, F, Fx, Fc, H, W, Co, KS, stream);
+}
+int cesm_stem_wgrad_mv(int dtype, const float* xt, const float* cond, const void* dy, float* dw, float* part, int nblk,
+                       int B, int V, int F, int Fx, int Fc, int H, int W, int Co, int KS, int accumulate,
+                       hipStream_t stream) {
+  return mv_stem_wgrad_launch(dtype, xt, cond, dy, dw, part, nblk, B, V, F, Fx, Fc, H, W, Co, KS, accumulate, stream);
+}
+int cesm_stem_dgrad_mv(int dtype, const void* dy, const float* w, float* dxt, float* dcond, int B, int V, int F, int Fx,
+                       int Fc, int H, int W, int Co, int KS, hipStream_t stream) {
+  return mv_stem_dgrad_launch(dtype, dy, w, dxt, dcond, B, V, F, Fx, Fc, H, W, Co, KS, stream);
+}
+int cesm_head_fwd_mv(int dtype, const void* x, const float* w, const float* bias, float* out, int B, int V, int F,
+                     int HW, int C, hipStream_t stream) {
+  return mv_head_fwd_launch(dtype, x, w, bias, out, B, V, F, HW, C, stream);
+}
+int cesm_head_bwd_mv(int dtype, const float* dout, const void* x, const float* w, void* dx, float* dw, float* db,
+                     float* part, int nblk, int B, int V, int F, int HW, int C, int accumulate, hipStream_t stream) {
+  return mv_head_bwd_launch(dtype, dout, x, w, dx, dw, db, part, nblk, B, V, F, HW, C, accumulate, stream);
 }
 
 int cesm_window_gather(const float* cond, const float* tgt, const int64_t* items, float* cwin, float* x0,

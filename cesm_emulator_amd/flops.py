@@ -68,8 +68,15 @@ def unet_forward_macs(net, F, H, W):
             macs += conv(up, h, w)
             h, w = h * 2, w * 2
     macs += resnet(net.out_conv[0], h, w)
-    macs += F * h * w * net.out_conv[1].weight.shape[1]
+    macs += stem_head_macs(net, F, h, w)[1]
     return macs
+
+
+def stem_head_macs(net, F, H, W):
+    """(stem, head) per-sample MACs: the two terms that depend on the number of target variables V (the stem has 2V
+    input channels, the head V output channels); both are part of unet_forward_macs."""
+    ws, wh = net.input_conv.weight, net.out_conv[1].weight
+    return F * H * W * ws.shape[0] * ws.shape[1] * ws.shape[-1] * ws.shape[-2], F * H * W * wh.shape[0] * wh.shape[1]
 
 
 def train_flops_per_sample(net, F, H, W):

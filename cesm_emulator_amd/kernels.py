@@ -238,60 +238,117 @@ def colsum(x, dst, accumulate=True):
     call("cesm_colsum", dtcode(x), P(x), P(dst), P(part), nsplit, rows, C, int(accumulate), S())
 
 
+def _mv_call(name, what, *args):
+    """a cesm_*_mv entry: CESM_EUNSUPPORTED (-2) is a ValueError that names the shape, any other failure a KernelError"""
+    rc = getattr(lib(), name)(*args)
+    if rc == -2:
+        raise ValueError(f"{name}: unsupported shape {what}")
+    if rc != 0:
+        raise KernelError(f"{name} failed with code {rc}")
+
+
+def _stem_io(xt, cond, cin, F):
+    """(B, V, Fx, Fc, H, W) of the stem's inputs, checked against the weight's input channels cin = 2V and the frame
+    count F.  xt [B, V, Fx, H, W], cond [B, V, Fc, H, W] fp32; at V = 1 the variable axis may be left out."""
+    if cin < 2 or cin % 2:
+        raise ValueError(f"stem weight with {cin} input channels: expected 2V (x_t and cond of V variables)")
+    V = cin // 2
+    if xt.ndim == 4 and cond.ndim == 4 and V == 1:
+        (B, Fx, H, W), Fc = xt.shape, cond.shape[1]
+        _chk(xt, dtype=torch.float32)
+        _chk(cond, (B, Fc, H, W), torch.float32)
+    else:
+        if xt.ndim != 5 or cond.ndim != 5:
+            raise ValueError(f"stem inputs must be [B, V, F, H, W], got {tuple(xt.shape)} and {tuple(cond.shape)}")
+        B, _, Fx, H, W = xt.shape
+        Fc = cond.shape[2]
+        _chk(xt, (B, V, Fx, H, W), torch.float32)
+        _chk(cond, (B, V, Fc, H, W), torch.float32)
+    if Fx not in (1, F) or Fc not in (1, F):
+        raise ValueError(f"stem: x_t has {Fx} frames and cond {Fc}; each must be 1 or F = {F}")
+    return B, V, Fx, Fc, H, W
+
+
 def stem_fwd(xt, cond, w, b, F, dtype):
-    B, Fx, H, W = xt.shape
-    Fc = cond.shape[1]
-    Co, _, _, KS, _ = w.shape
-    _chk(xt, dtype=torch.float32)
-    _chk(cond, (B, Fc, H, W), torch.float32)
+    """stem Conv3d(2V -> Co, (1,KS,KS)) on cat([x_t, cond]): w [Co, 2V, 1, KS, KS] gives V (1 <= V <= 4)"""
+    Co, cin, _, KS, _ = w.shape
+    B, V, Fx, Fc, H, W = _stem_io(xt, cond, cin, F)
+    _chk(w, (Co, cin, 1, KS, KS), torch.float32)
+    _chk(b, (Co,), torch.float32)
     y = empty((B * F, H, W, Co), dtype, xt.device)
-    call("cesm_stem_fwd", _DT[dtype], P(xt), P(cond), P(w), P(b), P(y), B, F, Fx, Fc, H, W, Co, KS, S())
+    _mv_call("cesm_stem_fwd_mv", f"V={V} KS={KS} Co={Co} F={F} Fx={Fx} Fc={Fc}", _DT[dtype], P(xt), P(cond), P(w), P(b),
+             P(y), B, V, F, Fx, Fc, H, W, Co, KS, S())
     return y
 
 
 def stem_wgrad(xt, cond, dy, dw, F, accumulate=True):
-    B, Fx, H, W = xt.shape
-    Fc = cond.shape[1]
-    Co = dy.shape[3]
-    KS = dw.shape[-1]
+    Co, cin, _, KS, _ = dw.shape
+    B, V, Fx, Fc, H, W = _stem_io(xt, cond, cin, F)
+    _chk(dy, (B * F, H, W, Co))
+    _chk(dw, (Co, cin, 1, KS, KS), torch.float32)
     nblk = 512
-    part = empty((nblk, Co * 2 * KS * KS), torch.float32, xt.device)
-    call("cesm_stem_wgrad", dtcode(dy), P(xt), P(cond), P(dy), P(dw), P(part), nblk, B, F, Fx, Fc, H, W, Co, KS,
-         int(accumulate), S())
+    part = empty((nblk, Co * cin * KS * KS), torch.float32, xt.device)
+    _mv_call("cesm_stem_wgrad_mv", f"V={V} KS={KS} Co={Co} F={F} Fx={Fx} Fc={Fc}", dtcode(dy), P(xt), P(cond), P(dy),
+             P(dw), P(part), nblk, B, V, F, Fx, Fc, H, W, Co, KS, int(accumulate), S())
 
 
 def stem_dgrad(dy, w, B, F, Fx, Fc, want_xt=True, want_cond=True):
-    """data gradient of the stem (csrc/stem_dgrad.h): dy [B*F, H, W, Co] (the tensor stem_wgrad reads), w the fp32
-    stem weight [Co, 2, 1, KS, KS].  Returns (dxt [B, Fx, H, W], dcond [B, Fc, H, W]) fp32, None where not wanted; an
-    input that was broadcast over frames (Fx or Fc == 1 < F) gets the sum over the F frames."""
+    """data gradient of the stem (csrc/stem_dgrad.h, csrc/multivar.h): dy [B*F, H, W, Co] (the tensor stem_wgrad reads),
+    w the fp32 stem weight [Co, 2V, 1, KS, KS].  Returns (dxt [B, V, Fx, H, W], dcond [B, V, Fc, H, W]) fp32 ([B, Fx, H,
+    W] and [B, Fc, H, W] at V = 1), None where not wanted; an input that was broadcast over frames (Fx or Fc == 1 < F)
+    gets the sum over the F frames."""
     Nb, H, W, Co = dy.shape
     KS = w.shape[-1]
+    cin = w.shape[1]
+    if cin < 2 or cin % 2:
+        raise ValueError(f"stem weight with {cin} input channels: expected 2V (x_t and cond of V variables)")
+    V = cin // 2
     _chk(dy, (B * F, H, W, Co))
-    _chk(w, (Co, 2, 1, KS, KS), torch.float32)
-    dxt = empty((B, Fx, H, W), torch.float32, dy.device) if want_xt else None
-    dcond = empty((B, Fc, H, W), torch.float32, dy.device) if want_cond else None
-    rc = lib().cesm_stem_dgrad(dtcode(dy), P(dy), P(w), P(dxt), P(dcond), B, F, Fx, Fc, H, W, Co, KS, S())
-    if rc == -2:  # CESM_EUNSUPPORTED
-        raise ValueError(f"stem_dgrad: unsupported shape KS={KS} Co={Co} F={F} Fx={Fx} Fc={Fc}")
-    if rc != 0:
-        raise KernelError(f"cesm_stem_dgrad failed with code {rc}")
+    _chk(w, (Co, cin, 1, KS, KS), torch.float32)
+    var = () if V == 1 else (V,)
+    dxt = empty((B, *var, Fx, H, W), torch.float32, dy.device) if want_xt else None
+    dcond = empty((B, *var, Fc, H, W), torch.float32, dy.device) if want_cond else None
+    _mv_call("cesm_stem_dgrad_mv", f"V={V} KS={KS} Co={Co} F={F} Fx={Fx} Fc={Fc}", dtcode(dy), P(dy), P(w), P(dxt),
+             P(dcond), B, V, F, Fx, Fc, H, W, Co, KS, S())
     return dxt, dcond
 
 
+def _head_v(w, C):
+    if w.numel() == 0 or w.numel() % C:
+        raise ValueError(f"head weight of shape {tuple(w.shape)} on {C} channels: expected [V, {C}]")
+    return w.numel() // C
+
+
 def head_fwd(x, w, b, B, F):
+    """head Conv3d(C -> V, 1) on frame F // 2: x [B*F, H, W, C], w [V, C] (any shape with V*C elements, e.g. the module's
+    [V, C, 1, 1, 1]), b [V]; returns [B, V, H, W] fp32"""
     Nb, H, W, C = x.shape
-    out = empty((B, 1, H, W), torch.float32, x.device)
-    call("cesm_head_fwd", dtcode(x), P(x), P(w), P(b), P(out), B, F, H * W, C, S())
+    V = _head_v(w, C)
+    _chk(x, (B * F, H, W, C))
+    _chk(w, dtype=torch.float32)
+    _chk(b, (V,), torch.float32)
+    out = empty((B, V, H, W), torch.float32, x.device)
+    _mv_call("cesm_head_fwd_mv", f"V={V} C={C}", dtcode(x), P(x), P(w), P(b), P(out), B, V, F, H * W, C, S())
     return out
 
 
 def head_bwd(dout, x, w, dw, db, B, F, need_dx=True, accumulate=True):
+    """dout [B, V, H, W] fp32; dw shaped like w ([V, C]), db [V] (both None: no parameter gradients)"""
     Nb, H, W, C = x.shape
+    V = _head_v(w, C)
+    _chk(x, (B * F, H, W, C))
+    _chk(dout, (B, V, H, W), torch.float32)
+    _chk(w, dtype=torch.float32)
+    if dw is not None:
+        _chk(dw, dtype=torch.float32)
+        _chk(db, (V,), torch.float32)
+        if dw.numel() != V * C or db is None:
+            raise RuntimeError(f"head_bwd: dw needs {V * C} elements and db [{V}]")
     dx = empty(x.shape, x.dtype, x.device) if need_dx else None
     nblk = 256
-    part = empty((nblk, C + 1), torch.float32, x.device)
-    call("cesm_head_bwd", dtcode(x), P(dout), P(x), P(w), P(dx), P(dw), P(db), P(part), nblk, B, F, H * W, C,
-         int(accumulate), S())
+    part = empty((nblk, V * (C + 1)), torch.float32, x.device)
+    _mv_call("cesm_head_bwd_mv", f"V={V} C={C}", dtcode(x), P(dout), P(x), P(w), P(dx), P(dw), P(db), P(part), nblk, B,
+             V, F, H * W, C, int(accumulate), S())
     return dx
 
 

@@ -61,8 +61,10 @@ class UNet(nn.Module):
         Fx, Fc = x_t.shape[2], cond.shape[2]
         if Fx != Fc and not (Fx == 1 or Fc == 1):
             raise ValueError(f"Frame mismatch: x_t F={Fx}, cond F={Fc}")
-        if x_t.shape[1] != 1 or cond.shape[1] != 1:
-            raise ValueError("single-variable model: x_t and cond need 1 channel")
+        V = self.net.n_vars
+        if x_t.shape[1] != V or cond.shape[1] != V:
+            raise ValueError(f"model with {V} target variable(s): x_t has {x_t.shape[1]} channels and cond "
+                             f"{cond.shape[1]}, both need {V}")
         if not x_t.is_cuda:
             raise RuntimeError("cesm_emulator_amd.UNet runs on the GPU only (move model and inputs to 'cuda')")
         if not torch.is_tensor(t):
@@ -73,11 +75,9 @@ class UNet(nn.Module):
         if t.shape[0] == 1 and x_t.shape[0] > 1:
             t = t.expand(x_t.shape[0]).contiguous()
         # frame-broadcast of model.py:111-118 happens inside the stem kernel (stride-0 read)
-        xt4 = x_t[:, 0].float().contiguous()
-        c4 = cond[:, 0].float().contiguous()
-        # the network's output is [B,1,F,H,W]; only frame F//2 is kept (model.py:124-130), so
+        # the network's output is [B,V,F,H,W]; only frame F//2 is kept (model.py:124-130), so
         # the 1x1 head conv is evaluated on that frame only.
-        return net_apply(self.net, xt4, c4, t)
+        return net_apply(self.net, x_t.float().contiguous(), cond.float().contiguous(), t)
 
 
 class _MSE(torch.autograd.Function):
@@ -302,7 +302,7 @@ class Diffusion(nn.Module):
 class GraphSampleStep:
     """One DDPM sampling step (model eval + fused update, in place on a static x) captured as a HIP graph
     (torch.cuda.graph drives hipStreamBeginCapture; every kernel launches on the capturing stream).
-    Static inputs: x [B,1,H,W] fp32 (updated in place), cond, t [B] int64, z (step noise; zero at t=0,
+    Static inputs: x [B,V,H,W] fp32 (updated in place), cond, t [B] int64, z (step noise; zero at t=0,
     where posterior_variance[0] = 0 makes the noise term vanish as in the reference's t=0 branch).
 
     ddim_eta=None is that DDPM step.  With ddim_eta >= 0 the captured update is the generalized DDIM step instead

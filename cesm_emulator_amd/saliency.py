@@ -1,7 +1,7 @@
 """Input gradients of the diffusion loss: which emissions (cond) and which noisy state (x_t) the prediction
 depends on.  The reference computes |d loss / d cond| during validation (train.py saliency_wrt_cond, plotted by
 quad_with_saliency); here the backward runs through the HIP network's dX chain and ends in the stem's data gradient
-(csrc/stem_dgrad.h), with every weight gradient left out.
+(csrc/stem_dgrad.h; csrc/multivar.h for several target variables), with every weight gradient left out.
 
 Both helpers leave the model as found: no p.grad is created or changed, no requires_grad flag is touched; they work on
 trainable and on frozen (checkpoint.load_checkpoint) models, in either compute_dtype.  A plain loss.backward() with
@@ -17,7 +17,7 @@ from .video_net import input_grads_only
 
 def input_grads(diffusion, x0, cond, t=None, noise=None):
     """(loss, d loss / d x_t, d loss / d cond) of the eps-prediction MSE at x_t = q_sample(x0, t, noise).
-    x0 [B,1,H,W]; cond [B,1,H,W] (F = 1) or a window [B,1,F,H,W]; t defaults to T // 2 for every sample.  The
+    x0 [B,V,H,W]; cond [B,V,H,W] (F = 1) or a window [B,V,F,H,W]; t defaults to T // 2 for every sample.  The
     gradients have x_t's (= x0's) and cond's shapes and are fp32; loss is detached."""
     B = x0.size(0)
     if t is None:
@@ -43,13 +43,13 @@ def counterfactual_delta(diffusion, cond, scale_mask=None, scale=1.1, steps=None
     halves get the same x_T and the same step noise (drawn for B samples, copied to the other half); the difference
     then isolates the change in cond."""
     cond2 = cond * scale if scale_mask is None else cond * (1.0 + (scale - 1.0) * scale_mask)
-    B, H, W = cond.shape[0], cond.shape[-2], cond.shape[-1]
+    B, V, H, W = cond.shape[0], cond.shape[1], cond.shape[-2], cond.shape[-1]  # V target variables, as cond has
     if paired:
-        x = diffusion._sample(torch.cat([cond, cond2], dim=0), (2 * B, 1, H, W), cond.device, None, None, None, steps,
+        x = diffusion._sample(torch.cat([cond, cond2], dim=0), (2 * B, V, H, W), cond.device, None, None, None, steps,
                               ddim_eta, True)
         return x[B:] - x[:B]
-    base = diffusion.sample(cond, (B, 1, H, W), cond.device, steps=steps, ddim_eta=ddim_eta)
-    pert = diffusion.sample(cond2, (B, 1, H, W), cond.device, steps=steps, ddim_eta=ddim_eta)
+    base = diffusion.sample(cond, (B, V, H, W), cond.device, steps=steps, ddim_eta=ddim_eta)
+    pert = diffusion.sample(cond2, (B, V, H, W), cond.device, steps=steps, ddim_eta=ddim_eta)
     return pert - base
 
 

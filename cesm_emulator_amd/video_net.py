@@ -132,6 +132,9 @@ class RunCtx:
 _PARAM_GRADS_OFF = [False]
 _INPUTS_ONLY = [False]
 
+# target variables the stem and head kernels take (csrc/multivar.h: 2V input planes, V head outputs)
+MAX_VARS = 4
+
 
 class input_grads_only:
     """Context: backwards of the HIP network started inside it compute the gradients of x_t / cond only -- no
@@ -658,8 +661,10 @@ class UNetModel3D(nn.Module):
         if not (use_temp_attn and cond_map) or day_cond or year_cond or use_mid_attn:
             raise NotImplementedError("only the configuration model.UNet builds is supported "
                                       "(temporal attention, cond map, no day/year cond, no mid attn)")
-        if n_vars != 1:
-            raise NotImplementedError("n_vars must be 1 (single target variable)")
+        if not 1 <= n_vars <= MAX_VARS:
+            raise NotImplementedError(f"n_vars must be 1 … {MAX_VARS} target variables (the stem and head kernels' "
+                                      f"limit), got {n_vars}")
+        self.n_vars = n_vars
         self.compute_dtype = torch.bfloat16
         in_ch = 2 * n_vars
         pad = init_kernel_size // 2
@@ -761,9 +766,9 @@ class UNetModel3D(nn.Module):
 
     # ---------------------------------------------------------------- executor
     def run_forward(self, x_t, cond, t, save):
-        """x_t [B,Fx,H,W], cond [B,Fc,H,W] fp32 (frame axis already squeezed), t int64 [B]."""
-        B, Fx, H, W = x_t.shape
-        F = max(Fx, cond.shape[1])
+        """x_t [B,V,Fx,H,W], cond [B,V,Fc,H,W] fp32, t int64 [B]; returns [B,V,H,W] (frame F//2)."""
+        B, _, Fx, H, W = x_t.shape
+        F = max(Fx, cond.shape[2])
         cdt = self.compute_dtype
         rc = RunCtx(self, B, F, cdt, save)
         rpb = self.time_rel_pos_bias
@@ -809,14 +814,14 @@ class UNetModel3D(nn.Module):
             tape.ups.append(s)
         x, tape.out_rb = resnet_fwd(rc, self.out_conv[0], x, r, None)
         head = self.out_conv[1]
-        out = K.head_fwd(x, head.weight.reshape(-1), head.bias, B, F)
+        out = K.head_fwd(x, head.weight, head.bias, B, F)
         tape.head_in = x
         return (out, tape) if save else out
 
     def backward_from(self, dout, tape, want_xt=False, want_cond=False, param_grads=True):
         """backward of the forward that recorded `tape` (held by that forward's autograd node, so several
         grad-enabled forwards may be in flight and each backward replays its own activations).  Returns (dxt, dcond):
-        the gradients of the forward's x_t [B,Fx,H,W] / cond [B,Fc,H,W] where asked for, else None.
+        the gradients of the forward's x_t [B,V,Fx,H,W] / cond [B,V,Fc,H,W] where asked for, else None.
         param_grads=False: no parameter gradient is computed (no p.grad created or changed, no readiness hook)."""
         if tape is None:
             raise RuntimeError("backward called twice for one forward (its tape was already consumed)")
@@ -841,8 +846,7 @@ class UNetModel3D(nn.Module):
         rc.dtable = gbuf(self.time_rel_pos_bias.relative_attention_bias.weight)
         head = self.out_conv[1]
         hw, hb = gbuf(head.weight), gbuf(head.bias)
-        dx = K.head_bwd(dout.contiguous(), tape.head_in, head.weight.reshape(-1),
-                        None if hw is None else hw.view(-1), hb, rc.B, rc.F)
+        dx = K.head_bwd(dout.contiguous(), tape.head_in, head.weight, hw, hb, rc.B, rc.F)
         dx, dr = resnet_bwd(rc, self.out_conv[0], tape.out_rb, dx)
         done(self.out_conv)
         nres = len(self.downs)
@@ -886,8 +890,11 @@ class UNetModel3D(nn.Module):
                 K.colsum(dx, bi)
         dxt = dcond = None
         if want_xt or want_cond:  # input gradients: the stem's data gradient, on the main stream
-            dxt, dcond = K.stem_dgrad(dx, self.input_conv.weight, rc.B, rc.F, tape.x_t.shape[1], tape.cond.shape[1],
+            dxt, dcond = K.stem_dgrad(dx, self.input_conv.weight, rc.B, rc.F, tape.x_t.shape[2], tape.cond.shape[2],
                                       want_xt, want_cond)
+            # kernels.stem_dgrad leaves the variable axis out at V = 1; the forward's inputs had it
+            dxt = None if dxt is None else dxt.view(tape.x_t.shape)
+            dcond = None if dcond is None else dcond.view(tape.cond.shape)
         # time MLP: temb = Lin3(SiLU(Lin1(emb)))
         l1, l3 = self.time_mlp[1], self.time_mlp[3]
         dh1 = torch.empty_like(tape.h1)

@@ -132,6 +132,24 @@ int cesm_head_fwd(int dtype, const void* x, const float* w, const float* bias, f
                   hipStream_t stream);
 int cesm_head_bwd(int dtype, const float* dout, const void* x, const float* w, void* dx, float* dw, float* db,
                   float* part, int nblk, int B, int F, int HW, int C, int accumulate, hipStream_t stream);
+/* The stem and head for V target variables, 1 <= V <= 4 (csrc/multivar.hip).  Tensors are the reference's:
+ * xt [B][V][Fx][H][W], cond [B][V][Fc][H][W], stem w [Co][2V][KS][KS] with input channels 0..V-1 = x_t and V..2V-1 =
+ * cond, dw the same shape, part nblk*Co*2V*KS*KS floats, dxt / dcond shaped like xt / cond (each nullable); head w
+ * [V][C], bias / db [V], out / dout [B][V][HW], dw [V][C], part nblk*V*(C+1) floats.  Everything else is as in the
+ * five entry points above, and V == 1 IS those entry points (same kernels, same grids).  CESM_EUNSUPPORTED for V
+ * outside 1..4 and for the stem shapes cesm_stem_dgrad refuses.  Deterministic.  (Added entry points: the ABI version
+ * stays.) */
+int cesm_stem_fwd_mv(int dtype, const float* xt, const float* cond, const float* w, const float* bias, void* y, int B,
+                     int V, int F, int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream);
+int cesm_stem_wgrad_mv(int dtype, const float* xt, const float* cond, const void* dy, float* dw, float* part, int nblk,
+                       int B, int V, int F, int Fx, int Fc, int H, int W, int Co, int KS, int accumulate,
+                       hipStream_t stream);
+int cesm_stem_dgrad_mv(int dtype, const void* dy, const float* w, float* dxt, float* dcond, int B, int V, int F, int Fx,
+                       int Fc, int H, int W, int Co, int KS, hipStream_t stream);
+int cesm_head_fwd_mv(int dtype, const void* x, const float* w, const float* bias, float* out, int B, int V, int F,
+                     int HW, int C, hipStream_t stream);
+int cesm_head_bwd_mv(int dtype, const float* dout, const void* x, const float* w, void* dx, float* dw, float* db,
+                     float* part, int nblk, int B, int V, int F, int HW, int C, int accumulate, hipStream_t stream);
 
 /* ---- normalisation (csrc/norm.hip) -------------------------------------------------------
  * GroupNorm(G,C) eps, affine, then x*(scale+1)+shift, SiLU, + residual: video_net.py:216-227, :265. */
