@@ -4,6 +4,7 @@ network op and for the AdamW step, RCCL data parallelism, device-side training-w
 """
 from .model import UNet, Diffusion  # noqa: F401
 from .optim import FusedAdamW  # noqa: F401
+from .ema import EMA, ema_decay  # noqa: F401
 from .saliency import counterfactual_delta, input_grads, saliency_wrt_cond  # noqa: F401
 
-__all__ = ["UNet", "Diffusion", "FusedAdamW", "input_grads", "saliency_wrt_cond", "counterfactual_delta"]
+__all__ = ["UNet", "Diffusion", "FusedAdamW", "EMA", "ema_decay", "input_grads", "saliency_wrt_cond", "counterfactual_delta"]

@@ -15,18 +15,23 @@ import torch
 from .model import UNet, Diffusion
 
 
-def save_checkpoint(path, diffusion, optimizer, epoch, config):
-    """train.py:1154-1165."""
+def save_checkpoint(path, diffusion, optimizer, epoch, config, ema=None):
+    """train.py:1154-1165.  ema (an ema.EMA): its state_dict() goes under a further top-level key "ema"; the
+    reference's readers index ckpt["model"] / use .get(...) and ignore it."""
     full = diffusion.state_dict()
     model_sd = {k[len("model."):]: v for k, v in full.items() if k.startswith("model.")}
     diff_buf = {k: v for k, v in full.items() if not k.startswith("model.")}
-    torch.save({"epoch": epoch, "model": model_sd, "diffusion_buffers": diff_buf,
-                "optimizer": optimizer.state_dict() if optimizer is not None else {}, "config": config}, path)
+    ckpt = {"epoch": epoch, "model": model_sd, "diffusion_buffers": diff_buf,
+            "optimizer": optimizer.state_dict() if optimizer is not None else {}, "config": config}
+    if ema is not None:
+        ckpt["ema"] = ema.state_dict()
+    torch.save(ckpt, path)
 
 
-def load_checkpoint(ckpt_path, unet, diffusion, optimizer=None, device="cuda"):
+def load_checkpoint(ckpt_path, unet, diffusion, optimizer=None, device="cuda", ema=None):
     """train.py:915-946: weights (strict=False, missing/unexpected keys reported as the reference does),
-    diffusion buffers, optimizer state; returns the epoch to resume at."""
+    diffusion buffers, optimizer state; returns the epoch to resume at.  ema (an ema.EMA): restored from the
+    checkpoint's "ema" entry; a checkpoint without one re-initialises it from the loaded weights, and says so."""
     ckpt = torch.load(ckpt_path, map_location=device, weights_only=True)
     missing, unexpected = unet.load_state_dict(ckpt["model"], strict=False)
     if missing or unexpected:
@@ -37,6 +42,12 @@ def load_checkpoint(ckpt_path, unet, diffusion, optimizer=None, device="cuda"):
     diffusion.load_state_dict(diff_state, strict=False)
     if optimizer is not None and ckpt.get("optimizer"):
         optimizer.load_state_dict(ckpt["optimizer"])
+    if ema is not None:
+        if ckpt.get("ema"):
+            ema.load_state_dict(ckpt["ema"])
+        else:
+            ema.reset_from_model()
+            print(f"[EMA] {ckpt_path} holds no EMA: re-initialised from the loaded weights.")
     start_epoch = int(ckpt.get("epoch", 0)) + 1
     print(f"[Resume] Loaded {ckpt_path}. Resuming at epoch {start_epoch}.")
     return start_epoch
@@ -54,13 +65,20 @@ def build_from_config(cfg, device):
     return unet, diffusion
 
 
-def load_diffusion_from_checkpoint(ckpt_path, device="cuda"):
-    """inference.py:47-73: returns (diffusion in eval mode with frozen parameters, config)."""
+def load_diffusion_from_checkpoint(ckpt_path, device="cuda", use_ema=False):
+    """inference.py:47-73: returns (diffusion in eval mode with frozen parameters, config).  use_ema=True loads the
+    EMA of the weights (ckpt["ema"]["model"]) instead of the raw ones; KeyError if the checkpoint has none."""
     dev = torch.device(device)
     ckpt = torch.load(ckpt_path, map_location=dev, weights_only=True)
     cfg = ckpt.get("config", {})
+    if use_ema:
+        if not ckpt.get("ema") or "model" not in ckpt["ema"]:
+            raise KeyError(f"{ckpt_path} holds no EMA of the weights (saved without ema=)")
+        weights = ckpt["ema"]["model"]
+    else:
+        weights = ckpt["model"]
     unet, diffusion = build_from_config(cfg, dev)
-    missing, unexpected = unet.load_state_dict(ckpt["model"], strict=False)
+    missing, unexpected = unet.load_state_dict(weights, strict=False)
     if missing or unexpected:
         print("[UNet] missing keys:", missing)
         print("[UNet] unexpected keys:", unexpected)

@@ -287,6 +287,100 @@ __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float
   }
 }
 
+// ---- AdamW step + EMA of the weights in the same pass (cesm_adamw_ema)
+// adamw_step_kernel plus the EMA bookkeeping, all of it only for a finite step: n = ++ema_n[0] counts the EMA
+// updates, ema_omd[0] = 1 - decay(n) is what the main kernel blends with; decay(n) = min(beta, (1+n)/(10+n)) with
+// warm-up, beta without, formed in double and rounded to fp32 once (ema.ema_decay is the host restatement).
+__global__ void adamw_ema_step_kernel(float* __restrict__ info, int* __restrict__ step, int* __restrict__ ema_n,
+                                      float* __restrict__ ema_omd, float beta, int warmup) {
+  if (threadIdx.x != 0) return;
+  const bool fin = info[2] != 0.f;
+  const int s = step[0] + (fin ? 1 : 0);
+  step[0] = s;
+  info[3] = (float)s;
+  if (!fin) return;
+  const int n = ema_n[0] + 1;
+  ema_n[0] = n;
+  double d = (double)beta;
+  if (warmup) {
+    const double w = (1.0 + (double)n) / (10.0 + (double)n);
+    d = w < d ? w : d;
+  }
+  ema_omd[0] = (float)(1.0 - d);
+}
+
+// One element of adamw_kernel (same expressions, same order) followed by the EMA blend with the parameter value just
+// formed: e += omd (p_new - e).  Every operation is rounded on its own (no FMA contraction), which is what
+// adamw_kernel's loop compiles to: there the packed multiplies and adds leave nothing to fuse.  Here the loop is laid
+// out differently (the g store sinks below the arithmetic) and the compiler would fuse g * coef - m; p, g, m and v
+// have to come out bit-identical to the plain step's, so contraction is off for this body.
+__device__ __forceinline__ void adamw_ema_elem(float& pe, float& ge, float& me, float& ve, float& ee, float coef,
+                                               int use_clip, float decay, float b1, float b2, float bc2_sqrt,
+                                               float eps, float step_size, float omd) {
+#pragma clang fp contract(off)
+  const float gr = ge * coef;
+  if (use_clip) ge = gr;
+  const float pv = pe * decay;
+  const float mv = me + (1.f - b1) * (gr - me);
+  const float vv = ve * b2 + (1.f - b2) * gr * gr;
+  me = mv;
+  ve = vv;
+  const float denom = sqrtf(vv) / bc2_sqrt + eps;
+  const float pn = pv - step_size * (mv / denom);
+  pe = pn;
+  ee = ee + omd * (pn - ee);
+}
+
+// VEC: 128-bit accesses over the first n / 4 * 4 elements (the host checks that all five pointers are 16-byte
+// aligned), the last n % 4 by the first threads of the grid; otherwise scalar grid-stride like adamw_kernel.
+template <bool VEC>
+__global__ void adamw_ema_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                 float* __restrict__ v, float* __restrict__ ema, const float* __restrict__ info,
+                                 const float* __restrict__ ema_omd, int64_t n, float lr, float b1, float b2, float eps,
+                                 float wd, int use_clip) {
+  if (info[2] == 0.f) return;  // non-finite loss/grad: no update, the EMA stays too
+  const float coef = use_clip ? info[1] : 1.f;
+  const float st = info[3];
+  const float bc1 = 1.f - powf(b1, st);
+  const float bc2_sqrt = sqrtf(1.f - powf(b2, st));
+  const float step_size = lr / bc1;
+  const float decay = 1.f - lr * wd;
+  const float omd = ema_omd[0];
+  const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if constexpr (VEC) {
+    const int64_t n4 = n / 4;
+    for (int64_t q = gid; q < n4; q += stride) {
+      float4 pq = reinterpret_cast<const float4*>(p)[q];
+      float4 gq = reinterpret_cast<const float4*>(g)[q];
+      float4 mq = reinterpret_cast<const float4*>(m)[q];
+      float4 vq = reinterpret_cast<const float4*>(v)[q];
+      float4 eq = reinterpret_cast<const float4*>(ema)[q];
+      adamw_ema_elem(pq.x, gq.x, mq.x, vq.x, eq.x, coef, use_clip, decay, b1, b2, bc2_sqrt, eps, step_size, omd);
+      adamw_ema_elem(pq.y, gq.y, mq.y, vq.y, eq.y, coef, use_clip, decay, b1, b2, bc2_sqrt, eps, step_size, omd);
+      adamw_ema_elem(pq.z, gq.z, mq.z, vq.z, eq.z, coef, use_clip, decay, b1, b2, bc2_sqrt, eps, step_size, omd);
+      adamw_ema_elem(pq.w, gq.w, mq.w, vq.w, eq.w, coef, use_clip, decay, b1, b2, bc2_sqrt, eps, step_size, omd);
+      if (use_clip) reinterpret_cast<float4*>(g)[q] = gq;
+      reinterpret_cast<float4*>(m)[q] = mq;
+      reinterpret_cast<float4*>(v)[q] = vq;
+      reinterpret_cast<float4*>(p)[q] = pq;
+      reinterpret_cast<float4*>(ema)[q] = eq;
+    }
+    const int64_t e = n4 * 4 + gid;  // tail: at most 3 elements
+    if (e < n) {
+      float ge = g[e];
+      adamw_ema_elem(p[e], ge, m[e], v[e], ema[e], coef, use_clip, decay, b1, b2, bc2_sqrt, eps, step_size, omd);
+      if (use_clip) g[e] = ge;
+    }
+  } else {
+    for (int64_t e = gid; e < n; e += stride) {
+      float ge = g[e];
+      adamw_ema_elem(p[e], ge, m[e], v[e], ema[e], coef, use_clip, decay, b1, b2, bc2_sqrt, eps, step_size, omd);
+      if (use_clip) g[e] = ge;
+    }
+  }
+}
+
 template <typename T>
 __global__ void add_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, int64_t n8) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n8; e += (int64_t)gridDim.x * blockDim.x) {
@@ -454,6 +548,23 @@ int cesm_adamw(float* p, float* g, float* m, float* v, float* info, int* step, i
   adamw_step_kernel<<<1, 64, 0, stream>>>(info, step);
   const unsigned grid = (unsigned)std::min<int64_t>(cdiv(n, 256), 8192);
   adamw_kernel<<<grid, 256, 0, stream>>>(p, g, m, v, info, n, lr, b1, b2, eps, wd, use_clip);
+  return cesm_launch_status();
+}
+
+int cesm_adamw_ema(float* p, float* g, float* m, float* v, float* info, int* step, int64_t n, float lr, float b1,
+                   float b2, float eps, float wd, int use_clip, float* ema, int* ema_n, float* ema_omd, float beta,
+                   int warmup, hipStream_t stream) {
+  if (!p || !g || !m || !v || !info || !step || !ema || !ema_n || !ema_omd || n < 1) return CESM_EINVAL;
+  adamw_ema_step_kernel<<<1, 64, 0, stream>>>(info, step, ema_n, ema_omd, beta, warmup);
+  const bool vec = n >= 4 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0;
+  if (vec) {
+    const unsigned grid = (unsigned)std::min<int64_t>(cdiv(n / 4, 256), 8192);
+    adamw_ema_kernel<true><<<grid, 256, 0, stream>>>(p, g, m, v, ema, info, ema_omd, n, lr, b1, b2, eps, wd, use_clip);
+  } else {
+    const unsigned grid = (unsigned)std::min<int64_t>(cdiv(n, 256), 8192);
+    adamw_ema_kernel<false><<<grid, 256, 0, stream>>>(p, g, m, v, ema, info, ema_omd, n, lr, b1, b2, eps, wd,
+                                                      use_clip);
+  }
   return cesm_launch_status();
 }
 

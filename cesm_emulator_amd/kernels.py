@@ -833,6 +833,32 @@ def adamw(p, g, m, v, info, lr, b1, b2, eps, wd, step_dev, use_clip):
          float(eps), float(wd), int(use_clip), S())
 
 
+def adamw_ema(p, g, m, v, info, lr, b1, b2, eps, wd, step_dev, use_clip, ema, ema_n, ema_omd, beta, warmup):
+    """adamw() plus, in the same launch, ema <- ema + (1 - decay) (p_new - ema) for a finite step.
+    ema: fp32 like p; ema_n: device int32 [1] count of EMA updates (advanced on device); ema_omd: device fp32 [1]
+    scratch; decay = min(beta, (1 + n) / (10 + n)) with warmup, beta without (ema.ema_decay)."""
+    beta = float(beta)
+    if not 0.0 <= beta < 1.0:
+        raise ValueError(f"beta must be in [0, 1), got {beta}")
+    for t in (p, g, m, v, info, step_dev, ema, ema_n, ema_omd):
+        if not torch.is_tensor(t):
+            raise TypeError(f"adamw_ema needs tensors, got {type(t).__name__}")
+    n = p.numel()
+    if p.ndim != 1 or n < 1:
+        raise ValueError(f"flat buffers must be 1-D and non-empty, got shape {tuple(p.shape)}")
+    for t in (p, g, m, v, ema):
+        _chk(t, (n,), torch.float32)
+    _chk(info, (4,), torch.float32)
+    _chk(step_dev, (1,), torch.int32)
+    _chk(ema_n, (1,), torch.int32)
+    _chk(ema_omd, (1,), torch.float32)
+    for t in (g, m, v, ema, info, step_dev, ema_n, ema_omd):
+        if t.device != p.device:
+            raise RuntimeError(f"tensors on different devices: {t.device} and {p.device}")
+    call("cesm_adamw_ema", P(p), P(g), P(m), P(v), P(info), P(step_dev), n, float(lr), float(b1), float(b2),
+         float(eps), float(wd), int(use_clip), P(ema), P(ema_n), P(ema_omd), beta, int(bool(warmup)), S())
+
+
 def cast(x, dtype):
     y = empty(x.shape, dtype, x.device)
     call("cesm_cast", dtcode(x), _DT[dtype], P(x), P(y), x.numel(), S())

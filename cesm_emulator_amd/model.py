@@ -29,6 +29,14 @@ class UNet(nn.Module):
                  use_temp_attn: bool = True, day_cond: bool = False, year_cond: bool = False,
                  cond_map: bool = True):
         super().__init__()
+        # what an identically shaped second instance is built from (ema.EMA's ema_model)
+        self.ctor_kwargs = dict(in_channels=in_channels, out_channels=out_channels, base_ch=base_ch,
+                                ch_mults=tuple(ch_mults), num_res_blocks=num_res_blocks, time_dim=time_dim,
+                                groups=groups, dropout=dropout, attn_heads=attn_heads, attn_dim_head=attn_dim_head,
+                                use_sparse_linear_attn=use_sparse_linear_attn, use_mid_attn=use_mid_attn,
+                                init_kernel_size=init_kernel_size, use_checkpoint=use_checkpoint,
+                                use_temp_attn=use_temp_attn, day_cond=day_cond, year_cond=year_cond,
+                                cond_map=cond_map)
         self.net = UNetModel3D(n_vars=out_channels, model_dim=base_ch, dim_mults=tuple(ch_mults),
                                attn_heads=attn_heads, attn_dim_head=attn_dim_head,
                                use_sparse_linear_attn=use_sparse_linear_attn, use_mid_attn=use_mid_attn,

@@ -81,6 +81,7 @@ class FusedAdamW:
         # (non-finite) step leaves bias corrections and the saved "step" consistent with exp_avg/exp_avg_sq
         self._step_dev = torch.zeros(1, dtype=torch.int32, device=self.flat.data.device)
         self.last_info = None  # device tensor: [norm, clip coef, finite, -]
+        self.ema = None  # an ema.EMA attaches itself here: step() then also updates it, in the same launch
         self.param_groups = [dict(params=self.flat.params, lr=self.lr, betas=self.betas, eps=self.eps,
                                   weight_decay=self.weight_decay)]
 
@@ -103,8 +104,14 @@ class FusedAdamW:
         if self.last_info is None or loss is not None:
             self.last_info = K.grad_norm(self.flat.grad, self.max_grad_norm or 0.0, loss)
         use_clip = bool(self.max_grad_norm)
-        K.adamw(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.last_info, lr, b1, b2,
-                g["eps"], g["weight_decay"], self._step_dev, use_clip)
+        ema = self.ema
+        if ema is None:
+            K.adamw(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.last_info, lr, b1, b2,
+                    g["eps"], g["weight_decay"], self._step_dev, use_clip)
+        else:  # the same step, and the EMA of the weights updated in the same launch (ema.py)
+            K.adamw_ema(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.last_info, lr, b1, b2,
+                        g["eps"], g["weight_decay"], self._step_dev, use_clip, ema.flat, ema._n_dev, ema._omd_dev,
+                        ema.beta, ema.warmup)
         self.last_info = None
         # parameters changed behind autograd's back: invalidate cached packed (bf16 / GEMM-layout) weights
         bump_param_epoch()

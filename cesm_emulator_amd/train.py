@@ -15,6 +15,7 @@ import torch
 
 from .model import UNet, Diffusion
 from .optim import FusedAdamW
+from .ema import EMA
 
 
 def build_model_from_config(cfg_unet):
@@ -56,6 +57,23 @@ def make_optimizer(diffusion, train_cfg):
                       weight_decay=opt.get("weight_decay", 1e-4), max_grad_norm=train_cfg.get("max_grad_norm", 1.0))
 
 
+def make_ema(diffusion, optimizer, train_cfg):
+    """The EMA of the weights the reference's loop expects (train.py:819, `ema=`), or None unless train_cfg["ema"] is
+    set: true for the defaults, or a dict with `beta` / `warmup`.  The shipped configs do not set it; it comes by
+    override or from the caller's dict.  The EMA attaches itself to the optimizer, whose step then updates it."""
+    cfg = train_cfg.get("ema")
+    if not cfg:
+        return None
+    if cfg is True:
+        cfg = {}
+    if not isinstance(cfg, dict):
+        raise TypeError(f"train.ema must be true or a mapping with beta / warmup, got {cfg!r}")
+    unknown = sorted(set(cfg) - {"beta", "warmup"})
+    if unknown:
+        raise ValueError(f"train.ema: unknown keys {unknown} (beta, warmup)")
+    return EMA(diffusion.model, optimizer, beta=cfg.get("beta", 0.9999), warmup=cfg.get("warmup", True))
+
+
 def train_step(diffusion, optimizer, x0, cond, max_grad_norm=1.0, dp=None, t=None, noise=None):
     """One optimizer step; returns the loss as a device tensor (no host sync)."""
     optimizer.zero_grad(set_to_none=True)
@@ -74,11 +92,22 @@ def train_step(diffusion, optimizer, x0, cond, max_grad_norm=1.0, dp=None, t=Non
     return loss.detach()
 
 
-def train_one_epoch(diffusion, dl, optimizer, device, max_grad_norm=1.0, use_amp=True, epoch=1, dp=None, seed=None):
+def train_one_epoch(diffusion, dl, optimizer, device, max_grad_norm=1.0, use_amp=True, epoch=1, dp=None, seed=None,
+                    ema=None):
     """train.py:808-911; returns the epoch's mean loss.  With dp (world > 1) and no generator set yet, each rank
-    draws t / eps from its own stream (dp_generator: base `seed`, or one broadcast from rank 0)."""
+    draws t / eps from its own stream (dp_generator: base `seed`, or one broadcast from rank 0).
+
+    ema (train.py:819): an ema.EMA attached to `optimizer`.  Its update happens inside optimizer.step(), in the AdamW
+    launch and only for an applied step, so this loop has no `ema.update()` to call; the argument is checked, and
+    ema_model follows use_amp.  Data-parallel runs need nothing more: after the gradient all-reduce every rank applies
+    the same step to the same weights, so the ranks' EMAs stay equal."""
+    if ema is not None and getattr(optimizer, "ema", None) is not ema:
+        raise ValueError("ema is not attached to this optimizer (EMA(model, optimizer) attaches it; was it detached, "
+                         "or built for another optimizer?)")
     diffusion.train()
     diffusion.model.compute_dtype = torch.bfloat16 if use_amp else torch.float32
+    if ema is not None and ema.ema_model.compute_dtype != diffusion.model.compute_dtype:
+        ema.ema_model.compute_dtype = diffusion.model.compute_dtype
     if dp is not None and getattr(dp, "world", 1) > 1 and diffusion.generator is None:
         diffusion.generator = dp_generator(device, dp, seed)
     total, steps = 0.0, 0

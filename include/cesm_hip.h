@@ -349,6 +349,18 @@ int cesm_grad_norm(const float* g, int64_t n, float max_norm, const float* loss,
  * corrections), so a skipped step leaves the count consistent with exp_avg / exp_avg_sq. */
 int cesm_adamw(float* p, float* g, float* m, float* v, float* info, int* step, int64_t n, float lr, float b1,
                float b2, float eps, float wd, int use_clip, hipStream_t stream);
+/* cesm_adamw plus an exponential moving average of the weights in the same pass over the flat buffers: p, g, m, v
+ * and step come out bit-identical to cesm_adamw's, and ema[i] <- ema[i] + omd (p_new[i] - ema[i]) in fp32 from the
+ * parameter value just written (no second read of p, no further launch).  For a finite step (info[2] != 0) the
+ * single-thread pre-kernel advances step / info[3] as cesm_adamw does, sets n = ++ema_n[0] (device count of EMA
+ * updates) and stores ema_omd[0] = (float)(1 - d), d = warmup ? min(beta, (1 + n) / (10 + n)) : beta in double; a
+ * skipped step leaves p, m, v, step, ema and ema_n untouched.  ema: [n] fp32; ema_n: device int; ema_omd: device
+ * scratch for one float; 0 <= beta < 1 (checked by the caller).  Any n >= 1 and any 4-byte alignment (128-bit
+ * accesses only where all five buffers are 16-byte aligned).  CESM_EINVAL on a null pointer or n < 1.
+ * An added entry point (no existing argument list changed): the ABI version stays, as for cesm_stem_dgrad. */
+int cesm_adamw_ema(float* p, float* g, float* m, float* v, float* info, int* step, int64_t n, float lr, float b1,
+                   float b2, float eps, float wd, int use_clip, float* ema, int* ema_n, float* ema_omd, float beta,
+                   int warmup, hipStream_t stream);
 /* out = a + b (gradient sums at residual / skip fan-outs) */
 int cesm_add(int dtype, const void* a, const void* b, void* out, int64_t n, hipStream_t stream);
 int cesm_cast(int dtype_in, int dtype_out, const void* x, void* y, int64_t n, hipStream_t stream);
