@@ -1,7 +1,7 @@
 // Small ops of the training step:
 //  * time embedding + small linears (video_net.py:101-113 SinusoidalPosEmb, :651-656 time_mlp,
 //    :238-242 ResnetBlock.mlp = SiLU -> Linear) — M = batch rows, fp32
-//  * diffusion q_sample + MSE loss and its gradient (model.py:196-208)
+//  * diffusion q_sample + MSE loss and its gradient (model.py:196-208); the latitude / min-SNR weighted loss
 //  * global grad-norm clip (torch/nn/utils/clip_grad.py:165-180) + fused AdamW
 //    (torch/optim/adam.py:417-547, decoupled weight decay) over one flat fp32 parameter buffer
 //  * dtype casts and the training-window gather (dataset_single_member.py:168-196)
@@ -221,6 +221,145 @@ __global__ void mse_bwd_kernel(const float* __restrict__ pred, const float* __re
   const float c = 2.f * gscale[0] / (float)n;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
     dpred[e] = c * (pred[e] - tgt[e]);
+}
+
+// ---- weighted loss (latitude weights x per-sample weights on one squared-error sum; cesm_wloss in cesm_hip.h)
+// The unit of work is one (b, v, h) row of W contiguous floats.  A block holds 256 / L row slots of L threads each
+// (L <= 256: the threads one row keeps busy, 16 bytes per thread on the VEC path); a thread's slot and its place in
+// the row are fixed for the whole launch, so the only integer divisions are the two per row that split the row index.
+struct WRow {
+  float w, ac;      // w[clamp(row0[b] + h)] and a[b] * ((1 - lam) + lam * w)
+  int64_t base;     // offset of the row's first element
+};
+
+__device__ __forceinline__ WRow wloss_row(int64_t r, const float* __restrict__ w, const int64_t* __restrict__ row0,
+                                          const float* __restrict__ a, float lam, int V, int H, int W, int Hg) {
+  const int64_t bv = r / H;
+  const int h = (int)(r - bv * H);
+  const int b = (int)(bv / V);
+  int64_t g = (row0 ? row0[b] : 0) + h;
+  g = g < 0 ? 0 : (g > Hg - 1 ? Hg - 1 : g);  // a wrong offset gives a wrong number, never a read outside w
+  WRow o;
+  o.w = w[g];
+  const float c = (1.f - lam) + lam * o.w;
+  o.ac = a ? a[b] * c : c;
+  o.base = r * W;
+  return o;
+}
+
+// part[blk][3] = the block's sums of d^2, w d^2 and a c d^2 (d = pred - noise); the weights meet a row's sum once
+template <bool VEC>
+__global__ __launch_bounds__(256) void wloss_partial_kernel(const float* __restrict__ pred,
+                                                            const float* __restrict__ noise,
+                                                            const float* __restrict__ w,
+                                                            const int64_t* __restrict__ row0,
+                                                            const float* __restrict__ a, float lam,
+                                                            float* __restrict__ part, int64_t R, int V, int H, int W,
+                                                            int Hg, int L) {
+  __shared__ float red[4][3];
+  const int slot = (int)threadIdx.x / L, li = (int)threadIdx.x - slot * L, slots = 256 / L;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  if (slot < slots) {
+    for (int64_t r = (int64_t)blockIdx.x * slots + slot; r < R; r += (int64_t)gridDim.x * slots) {
+      const WRow row = wloss_row(r, w, row0, a, lam, V, H, W, Hg);
+      const float* p = pred + row.base;
+      const float* q = noise + row.base;
+      float rs = 0.f;
+      if (VEC) {
+        for (int e = li; e < (W >> 2); e += L) {
+          float pv[4], qv[4];
+          load4(p + e * 4, pv);
+          load4(q + e * 4, qv);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float d = pv[i] - qv[i];
+            rs = fmaf(d, d, rs);
+          }
+        }
+      } else {
+        for (int e = li; e < W; e += L) {
+          const float d = p[e] - q[e];
+          rs = fmaf(d, d, rs);
+        }
+      }
+      s0 += rs;
+      s1 = fmaf(row.w, rs, s1);
+      s2 = fmaf(row.ac, rs, s2);
+    }
+  }
+  s0 = wave_sum(s0), s1 = wave_sum(s1), s2 = wave_sum(s2);
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) red[wv][0] = s0, red[wv][1] = s1, red[wv][2] = s2;
+  __syncthreads();
+  if (threadIdx.x < 3)
+    part[blockIdx.x * 3 + threadIdx.x] =
+        ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// out = {mse_raw, mse_lat, total}: the block partials added in double in a fixed order by ONE wave -- lane l adds the
+// partials of blocks l, l + 64, ... in that order, then the lanes' sums meet in wave_sum_d's butterfly.  (One thread
+// walking all 512 partials, as mse_final_kernel does, measured 41 us here against 5 us for the partial kernel.)
+__global__ __launch_bounds__(64) void wloss_final_kernel(const float* __restrict__ part, float* __restrict__ out,
+                                                         int nblk, int64_t n) {
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (int k = threadIdx.x; k < nblk; k += 64) {
+    s0 += part[k * 3], s1 += part[k * 3 + 1], s2 += part[k * 3 + 2];
+  }
+  s0 = wave_sum_d(s0), s1 = wave_sum_d(s1), s2 = wave_sum_d(s2);
+  if (threadIdx.x == 0) {
+    out[0] = (float)(s0 / (double)n);
+    out[1] = (float)(s1 / (double)n);
+    out[2] = (float)(s2 / (double)n);
+  }
+}
+
+// dpred = gscale[0] (2 / n) a[b] c(b, h) (pred - noise)
+template <bool VEC>
+__global__ __launch_bounds__(256) void wloss_bwd_kernel(const float* __restrict__ pred,
+                                                        const float* __restrict__ noise,
+                                                        const float* __restrict__ w,
+                                                        const int64_t* __restrict__ row0,
+                                                        const float* __restrict__ a, float lam,
+                                                        const float* __restrict__ gscale, float* __restrict__ dpred,
+                                                        int64_t R, int V, int H, int W, int Hg, int L) {
+  const int slot = (int)threadIdx.x / L, li = (int)threadIdx.x - slot * L, slots = 256 / L;
+  if (slot >= slots) return;
+  const float sc = 2.f * gscale[0] / (float)(R * W);
+  for (int64_t r = (int64_t)blockIdx.x * slots + slot; r < R; r += (int64_t)gridDim.x * slots) {
+    const WRow row = wloss_row(r, w, row0, a, lam, V, H, W, Hg);
+    const float k = sc * row.ac;
+    const float* p = pred + row.base;
+    const float* q = noise + row.base;
+    float* o = dpred + row.base;
+    if (VEC) {
+      for (int e = li; e < (W >> 2); e += L) {
+        float pv[4], qv[4], dv[4];
+        load4(p + e * 4, pv);
+        load4(q + e * 4, qv);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dv[i] = k * (pv[i] - qv[i]);
+        store4(o + e * 4, dv);
+      }
+    } else {
+      for (int e = li; e < W; e += L) o[e] = k * (p[e] - q[e]);
+    }
+  }
+}
+
+// the launch shape of the weighted-loss kernels: L threads per row slot and the grid, at most 512 blocks
+struct WLossGeom {
+  bool vec;
+  int L;
+  unsigned grid;
+};
+bool wloss_geom(int B, int V, int H, int W, int Hg, float lam, uintptr_t ptrs, WLossGeom* g) {
+  if (B < 1 || V < 1 || H < 1 || W < 1 || Hg < H || !(lam >= 0.f && lam <= 1.f)) return false;
+  g->vec = W % 4 == 0 && (ptrs & 15) == 0;
+  const int units = g->vec ? W / 4 : W;       // accesses per row
+  const int passes = (int)cdiv(units, 256);   // a row longer than the block takes several, evenly filled
+  g->L = (int)cdiv(units, passes);
+  g->grid = (unsigned)std::min<int64_t>(cdiv((int64_t)B * V * H, 256 / g->L), 512);
+  return true;
 }
 
 // ---- grad norm + clip + AdamW over flat fp32 buffers
@@ -530,6 +669,37 @@ int cesm_mse_bwd(const float* pred, const float* tgt, const float* gscale, float
                  hipStream_t stream) {
   const unsigned grid = (unsigned)std::min<int64_t>(cdiv(n, 256), 4096);
   mse_bwd_kernel<<<grid, 256, 0, stream>>>(pred, tgt, gscale, dpred, n);
+  return cesm_launch_status();
+}
+
+// out[3] = {mse_raw, mse_lat, total}; part: 512 * 3 floats
+int cesm_wloss(const float* pred, const float* noise, const float* w, const int64_t* row0, const float* a, float lam,
+               float* out, float* part, int B, int V, int H, int W, int Hg, hipStream_t stream) {
+  WLossGeom g;
+  if (!pred || !noise || !w || !out || !part) return CESM_EINVAL;
+  if (!wloss_geom(B, V, H, W, Hg, lam, (uintptr_t)pred | (uintptr_t)noise, &g)) return CESM_EINVAL;
+  const int64_t R = (int64_t)B * V * H;
+  if (g.vec)
+    wloss_partial_kernel<true><<<g.grid, 256, 0, stream>>>(pred, noise, w, row0, a, lam, part, R, V, H, W, Hg, g.L);
+  else
+    wloss_partial_kernel<false><<<g.grid, 256, 0, stream>>>(pred, noise, w, row0, a, lam, part, R, V, H, W, Hg, g.L);
+  wloss_final_kernel<<<1, 64, 0, stream>>>(part, out, (int)g.grid, R * W);
+  return cesm_launch_status();
+}
+
+int cesm_wloss_bwd(const float* pred, const float* noise, const float* w, const int64_t* row0, const float* a,
+                   float lam, const float* gscale, float* dpred, int B, int V, int H, int W, int Hg,
+                   hipStream_t stream) {
+  WLossGeom g;
+  if (!pred || !noise || !w || !gscale || !dpred) return CESM_EINVAL;
+  if (!wloss_geom(B, V, H, W, Hg, lam, (uintptr_t)pred | (uintptr_t)noise | (uintptr_t)dpred, &g)) return CESM_EINVAL;
+  const int64_t R = (int64_t)B * V * H;
+  if (g.vec)
+    wloss_bwd_kernel<true><<<g.grid, 256, 0, stream>>>(pred, noise, w, row0, a, lam, gscale, dpred, R, V, H, W, Hg,
+                                                       g.L);
+  else
+    wloss_bwd_kernel<false><<<g.grid, 256, 0, stream>>>(pred, noise, w, row0, a, lam, gscale, dpred, R, V, H, W, Hg,
+                                                        g.L);
   return cesm_launch_status();
 }
 

@@ -97,6 +97,12 @@ class WindowSampler:
         return np.asarray([self.item(int(k)) for k in indices], dtype=np.int64).reshape(-1, 6)
 
 
+def row0_of(items):
+    """the crop row offsets of item rows (column 4: the grid row of each sample's row 0; zeros without a crop) as an
+    int64 CPU tensor [n] -- what Diffusion.loss(..., row0=) takes"""
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(items, dtype=np.int64).reshape(-1, 6)[:, 4]))
+
+
 def host_gather(cond, tgt, items, K, h, w, center, out_c, out_x):
     """Host-side batch assembly for the pinned path: out_c [n,1,K,h,w], out_x [n,1,h,w] (numpy
     views of pinned buffers) from (T,M,H,W) fields and item rows (t0, m, anchor, rev, i, j)."""
@@ -131,7 +137,8 @@ def shard_indices(n, batch_size, rank=0, world=1, shuffle=True, seed=0, epoch=0,
 
 
 class DeviceWindowLoader:
-    """HBM-resident fields + device gather kernel; iterate -> (cond [B,1,K,h,w], x0 [B,1,h,w])."""
+    """HBM-resident fields + device gather kernel; iterate -> (cond [B,1,K,h,w], x0 [B,1,h,w]).
+    last_row0: the crop row offsets (row0_of) of the batch last yielded."""
 
     def __init__(self, cond, tgt, K, batch_size, device, center=True, crop_hw=None, crop_mode="random",
                  time_reverse_p=0.5, shuffle=True, seed=0, rank=0, world=1):
@@ -147,6 +154,7 @@ class DeviceWindowLoader:
         self.shuffle, self.seed, self.rank, self.world = shuffle, seed, rank, world
         self.epoch = 0
         self._items_host = torch.empty((batch_size, 6), dtype=torch.int64).pin_memory()
+        self.last_row0 = torch.zeros(0, dtype=torch.int64)
 
     def set_epoch(self, e):
         self.epoch = e
@@ -156,6 +164,7 @@ class DeviceWindowLoader:
 
     def batch(self, indices):
         it = self.sampler.items(indices)
+        self.last_row0 = row0_of(it)
         n = it.shape[0]
         host = self._items_host[:n]
         host.copy_(torch.from_numpy(it))
@@ -171,7 +180,8 @@ class DeviceWindowLoader:
 
 
 class PinnedWindowLoader:
-    """Host-resident fields; host gather into pinned double-buffers, H2D on a side stream."""
+    """Host-resident fields; host gather into pinned double-buffers, H2D on a side stream.
+    last_row0: the crop row offsets (row0_of) of the batch last yielded, not of the one being prefetched."""
 
     def __init__(self, cond, tgt, K, batch_size, device, center=True, crop_hw=None, crop_mode="random",
                  time_reverse_p=0.5, shuffle=True, seed=0, rank=0, world=1):
@@ -192,6 +202,7 @@ class PinnedWindowLoader:
         self.dev = [(torch.empty((batch_size, 1, K, h, w), device=device),
                      torch.empty((batch_size, 1, h, w), device=device)) for _ in range(2)]
         self.done = [None, None]
+        self.last_row0 = torch.zeros(0, dtype=torch.int64)
 
     def set_epoch(self, e):
         self.epoch = e
@@ -222,15 +233,16 @@ class PinnedWindowLoader:
                 ev = torch.cuda.Event()
                 ev.record(self.stream)
             self.done[slot] = ev
-            return slot, n
+            return slot, n, row0_of(items)
 
         if not batches:
             return
         pending = issue(0)
         for k in range(len(batches)):
-            slot, n = pending
+            slot, n, row0 = pending
             main.wait_event(self.done[slot])
             if k + 1 < len(batches):
                 pending = issue(k + 1)  # overlaps the consumer's compute on batch k
             dc, dx = self.dev[slot]
+            self.last_row0 = row0
             yield dc[:n], dx[:n]

@@ -819,6 +819,45 @@ def mse_bwd(pred, tgt, gscale):
     return d
 
 
+def _wloss_args(pred, noise, w, row0, a, lam):
+    """checks shared by wloss / wloss_bwd; returns (B, V, H, W, Hg, lam)"""
+    _chk(pred, dtype=torch.float32)
+    if pred.ndim != 4:
+        raise RuntimeError(f"shape mismatch: pred must be [B, V, H, W], got {tuple(pred.shape)}")
+    B, V, H, W = pred.shape
+    _chk(noise, pred.shape, torch.float32)
+    _chk(w, dtype=torch.float32)
+    if w is None or w.ndim != 1 or w.numel() < H:
+        raise RuntimeError(f"shape mismatch: w must be [Hg] with Hg >= H = {H}")
+    _chk(row0, (B,), torch.int64)
+    _chk(a, (B,), torch.float32)
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lam must be in [0, 1], got {lam}")
+    return B, V, H, W, w.numel(), lam
+
+
+def wloss(pred, noise, w, row0, a, lam):
+    """Weighted squared-error loss (cesm_wloss): [3] device tensor {mse_raw, mse_lat, total} of d = pred - noise
+    [B, V, H, W] with row weights w [Hg], crop row offsets row0 [B] int64 (None: 0), per-sample weights a [B]
+    (None: 1) and blend lam; total = mean(a[b] ((1 - lam) + lam w[row0[b] + h]) d^2).  row0 is a device tensor and is
+    not range-checked here (the kernel clamps the row index into w; the caller validates)."""
+    B, V, H, W, Hg, lam = _wloss_args(pred, noise, w, row0, a, lam)
+    out = empty((3,), torch.float32, pred.device)
+    part = empty((512 * 3,), torch.float32, pred.device)
+    call("cesm_wloss", P(pred), P(noise), P(w), P(row0), P(a), lam, P(out), P(part), B, V, H, W, Hg, S())
+    return out
+
+
+def wloss_bwd(pred, noise, w, row0, a, lam, gscale):
+    """d total / d pred of wloss, times gscale[0] (device fp32 [1])"""
+    B, V, H, W, Hg, lam = _wloss_args(pred, noise, w, row0, a, lam)
+    _chk(gscale, (1,), torch.float32)
+    d = empty(pred.shape, torch.float32, pred.device)
+    call("cesm_wloss_bwd", P(pred), P(noise), P(w), P(row0), P(a), lam, P(gscale), P(d), B, V, H, W, Hg, S())
+    return d
+
+
 def grad_norm(flat_grad, max_norm, loss=None):
     info = empty((4,), torch.float32, flat_grad.device)
     part = empty((1024,), torch.float64, flat_grad.device)

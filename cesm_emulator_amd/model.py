@@ -10,6 +10,7 @@ the CPU fp32 reference within 1e-5 relative L2).
 """
 from __future__ import annotations
 
+import numbers
 import os
 
 import torch
@@ -100,16 +101,70 @@ class _MSE(torch.autograd.Function):
         return K.mse_bwd(pred, noise, g.reshape(1).contiguous()), None
 
 
-class Diffusion(nn.Module):
-    """model.py:141-208 — linear β schedule (1e-4 → 2e-2), ε-prediction MSE."""
+class _WLoss(torch.autograd.Function):
+    """K.wloss as three 0-d outputs (mse_raw, mse_lat, total); only total is differentiable, and only in pred"""
 
-    def __init__(self, model, img_channels=1, timesteps=1000, beta_schedule="linear"):
+    @staticmethod
+    def forward(ctx, pred, noise, w, row0, a, lam):
+        ctx.save_for_backward(pred, noise, w, row0, a)
+        ctx.lam = lam
+        out = K.wloss(pred, noise, w, row0, a, lam)
+        raw, lat, total = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(raw, lat)
+        return raw, lat, total
+
+    @staticmethod
+    def backward(ctx, g_raw, g_lat, g):
+        pred, noise, w, row0, a = ctx.saved_tensors
+        d = K.wloss_bwd(pred, noise, w, row0, a, ctx.lam, g.reshape(1).contiguous())
+        return d, None, None, None, None, None
+
+
+def latitude_weights(lat):
+    """Row weights of a regular lat-lon grid from its latitudes in degrees: clamp_min(cos(lat), 0) / (mean + 1e-8),
+    in float64 on the host, rounded to fp32 once (a CPU tensor [Hg])."""
+    lat = torch.as_tensor(lat, dtype=torch.float64, device="cpu").reshape(-1)
+    w = torch.cos(torch.deg2rad(lat)).clamp_min(0.0)
+    return (w / (w.mean() + 1e-8)).float()
+
+
+def min_snr_weights(alphas_cumprod, gamma):
+    """Min-SNR-gamma weights of an eps-prediction loss (Hang et al. 2023): a_t = min(SNR_t, gamma) / SNR_t =
+    min(1, gamma (1 - ac_t) / ac_t), in float64 from the fp32 alphas_cumprod entries, rounded to fp32 once."""
+    ac = alphas_cumprod.double()
+    return (gamma * (1.0 - ac) / ac).clamp_max(1.0).float()
+
+
+class Diffusion(nn.Module):
+    """model.py:141-208 — linear β schedule (1e-4 → 2e-2), ε-prediction MSE.
+
+    Weighted loss (both off by default, which leaves loss() as it was):
+      lat_weight   lam in [0, 1]: every grid row h weighs (1 - lam) + lam w[h], w = latitude_weights(lat);
+      min_snr_gamma   None or gamma > 0: sample b weighs min(1, gamma (1 - ac_t) / ac_t) at its timestep t;
+      lat   latitudes in degrees of the FULL grid's rows (length Hg), or None: then the tensor's own H rows span
+            linspace(-90, 90, H), as the reference's _latitude_weights, and a crop offset makes no sense.
+    The weights are normalised over the full grid, so an equatorial crop weighs more than a polar one."""
+
+    def __init__(self, model, img_channels=1, timesteps=1000, beta_schedule="linear", lat_weight=0.0,
+                 min_snr_gamma=None, lat=None):
         super().__init__()
         self.model = model
         self.img_channels = img_channels
         self.T = timesteps
         if beta_schedule != "linear":
             raise ValueError("Only 'linear' beta_schedule implemented")
+        self.lat_weight = float(lat_weight)
+        if not 0.0 <= self.lat_weight <= 1.0:
+            raise ValueError(f"lat_weight must be in [0, 1], got {lat_weight}")
+        if min_snr_gamma is not None:
+            if isinstance(min_snr_gamma, bool) or not isinstance(min_snr_gamma, numbers.Real) or not min_snr_gamma > 0:
+                raise ValueError(f"min_snr_gamma must be None or a number > 0, got {min_snr_gamma!r}")
+            min_snr_gamma = float(min_snr_gamma)
+        self.min_snr_gamma = min_snr_gamma
+        self._lat = None if lat is None else torch.as_tensor(lat, dtype=torch.float64, device="cpu").reshape(-1)
+        if self._lat is not None and self._lat.numel() < 1:
+            raise ValueError("lat must hold the latitude of every grid row")
+        self._lat_w = {}  # (Hg, device) -> fp32 row weights
         betas = torch.linspace(1e-4, 2e-2, timesteps)
         alphas = 1.0 - betas
         ac = torch.cumprod(alphas, dim=0)
@@ -122,10 +177,18 @@ class Diffusion(nn.Module):
         self.register_buffer("sqrt_one_minus_alphas_cumprod", torch.sqrt(1.0 - ac))
         self.register_buffer("sqrt_recip_alphas", torch.sqrt(1.0 / alphas))
         self.register_buffer("posterior_variance", betas * (1.0 - acp) / (1.0 - ac))
+        # not part of state_dict(): checkpoints keep the reference's 8 buffers
+        self.register_buffer("min_snr_weight", None if min_snr_gamma is None else min_snr_weights(ac, min_snr_gamma),
+                             persistent=False)
         # draws of t / eps in loss(): None = the default generator (as model.py:205-206); data-parallel
         # training gives every rank its own stream (train.rank_generator) so ranks do not draw identical
         # t / eps for their different samples
         self.generator = None
+
+    @property
+    def weighted(self):
+        """whether loss() is the weighted loss (loss_components()['total']) and not the plain mean"""
+        return self.lat_weight != 0.0 or self.min_snr_gamma is not None
 
     def q_sample(self, x0, t, noise=None):
         if noise is None:
@@ -134,8 +197,8 @@ class Diffusion(nn.Module):
                         self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
         return xt, noise
 
-    def loss(self, x0, cond, t=None, noise=None):
-        """model.py:203-208; optional t / noise make the draw reproducible for parity tests."""
+    def _eps(self, x0, cond, t, noise):
+        """the draws of loss() (t, then noise, on self.generator) and the network's eps for them"""
         B = x0.size(0)
         g = self.generator
         if t is None:
@@ -143,8 +206,63 @@ class Diffusion(nn.Module):
         if noise is None:
             noise = torch.randn(x0.shape, device=x0.device, dtype=x0.dtype, generator=g)
         x_t, noise = self.q_sample(x0, t, noise)
-        eps = self.model(x_t, cond, t)
-        return _MSE.apply(eps, noise.float().contiguous())
+        return self.model(x_t, cond, t), noise.float().contiguous(), t
+
+    def loss(self, x0, cond, t=None, noise=None, row0=None):
+        """model.py:203-208; optional t / noise make the draw reproducible for parity tests.  With lat_weight or
+        min_snr_gamma set this is loss_components(...)['total'] (row0: see there), else the plain mean."""
+        if self.weighted:
+            return self.loss_components(x0, cond, t=t, noise=noise, row0=row0)["total"]
+        eps, noise, _ = self._eps(x0, cond, t, noise)
+        return _MSE.apply(eps, noise)
+
+    def lat_weights(self, H, device):
+        """fp32 row weights [Hg] on `device` (latitude_weights of `lat`, or of linspace(-90, 90, H) without one),
+        cached per (Hg, device)"""
+        if self._lat is not None and self._lat.numel() < H:
+            raise ValueError(f"lat has {self._lat.numel()} rows, the batch {H}")
+        Hg = H if self._lat is None else self._lat.numel()
+        key = (Hg, torch.device(device))
+        w = self._lat_w.get(key)
+        if w is None:
+            lat = torch.linspace(-90.0, 90.0, Hg, dtype=torch.float64) if self._lat is None else self._lat
+            w = self._lat_w[key] = latitude_weights(lat).to(device)
+        return w
+
+    def _row0(self, row0, B, H, Hg, device):
+        """row0 as a device int64 [B] tensor (None stays None).  A list or CPU tensor is range-checked here; a device
+        tensor is NOT read back (no synchronisation): the kernel's clamp of the row index is its only guard, so a
+        wrong device row0 gives a wrong loss, never a fault."""
+        if row0 is None:
+            return None
+        if torch.is_tensor(row0) and row0.is_cuda:
+            return row0.to(device=device, dtype=torch.long).contiguous()
+        r = torch.as_tensor(row0, dtype=torch.long).reshape(-1)
+        if r.numel() != B:
+            raise ValueError(f"row0 needs one entry per sample ({B}), got {r.numel()}")
+        if bool(((r < 0) | (r + H > Hg)).any()):
+            hint = " (no `lat` given: the batch is the whole grid, so row0 must be 0)" if self._lat is None else ""
+            raise ValueError(f"row0 must satisfy 0 <= row0 and row0 + H <= Hg with H = {H}, Hg = {Hg}, got "
+                             f"{r.tolist()}{hint}")
+        return r.to(device)
+
+    def loss_components(self, x0, cond, t=None, noise=None, row0=None):
+        """The reference training loop's hook (train.py:836-841): {'mse_raw', 'mse_lat', 'cond_loss', 'total'} as 0-d
+        device tensors from one weighted-loss kernel (csrc/misc.hip cesm_wloss; formulas in include/cesm_hip.h).
+        `total` is differentiable; the others are detached, cond_loss is a zero.  RNG use is that of loss().
+
+        row0: the grid row of each sample's row 0 (crops; DeviceWindowLoader.last_row0), [B]; None: 0.  A list or CPU
+        tensor is validated (0 <= row0, row0 + H <= Hg, else ValueError before anything is launched); a CUDA int64
+        tensor is not synchronised on (see _row0)."""
+        if x0.ndim != 4:
+            raise ValueError(f"x0 must be [B, V, H, W], got {tuple(x0.shape)}")
+        B, H = x0.shape[0], x0.shape[2]
+        w = self.lat_weights(H, x0.device)
+        row0 = self._row0(row0, B, H, w.numel(), x0.device)
+        eps, noise, t = self._eps(x0, cond, t, noise)
+        a = None if self.min_snr_weight is None else self.min_snr_weight[t]
+        raw, lat, total = _WLoss.apply(eps, noise, w, row0, a, self.lat_weight)
+        return {"mse_raw": raw, "mse_lat": lat, "cond_loss": torch.zeros((), device=x0.device), "total": total}
 
     def _coefs(self):
         return self.sqrt_recip_alphas, self.betas, self.sqrt_one_minus_alphas_cumprod, self.posterior_variance

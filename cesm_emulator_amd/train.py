@@ -74,14 +74,42 @@ def make_ema(diffusion, optimizer, train_cfg):
     return EMA(diffusion.model, optimizer, beta=cfg.get("beta", 0.9999), warmup=cfg.get("warmup", True))
 
 
-def train_step(diffusion, optimizer, x0, cond, max_grad_norm=1.0, dp=None, t=None, noise=None):
-    """One optimizer step; returns the loss as a device tensor (no host sync)."""
+def make_diffusion(unet, train_cfg, lat=None):
+    """The Diffusion of a training config: `timesteps`, `beta_schedule` and an optional
+    train_cfg["loss"] = {"lat_weight": …, "min_snr_gamma": …} (the weighted loss; the shipped configs do not set it).
+    lat: latitudes in degrees of the full grid's rows, from the data (Diffusion's `lat`)."""
+    cfg = train_cfg.get("loss") or {}
+    if not isinstance(cfg, dict):
+        raise TypeError(f"train.loss must be a mapping with lat_weight / min_snr_gamma, got {cfg!r}")
+    unknown = sorted(set(cfg) - {"lat_weight", "min_snr_gamma"})
+    if unknown:
+        raise ValueError(f"train.loss: unknown keys {unknown} (lat_weight, min_snr_gamma)")
+    return Diffusion(unet, img_channels=1, timesteps=train_cfg.get("timesteps", 1000),
+                     beta_schedule=train_cfg.get("beta_schedule", "linear"), lat_weight=cfg.get("lat_weight", 0.0),
+                     min_snr_gamma=cfg.get("min_snr_gamma"), lat=lat)
+
+
+def train_step(diffusion, optimizer, x0, cond, max_grad_norm=1.0, dp=None, t=None, noise=None, row0=None,
+               return_components=False):
+    """One optimizer step; returns the loss as a device tensor (no host sync).  row0: the batch's crop row offsets
+    for a weighted loss (Diffusion.loss_components).  return_components=True returns (loss, comps) instead, comps a
+    [4] device tensor ordered mse_raw, mse_lat, cond_loss, total (the plain loss: loss, loss, 0, loss); the step is
+    taken on total either way."""
     optimizer.zero_grad(set_to_none=True)
     net = diffusion.model.net
     overlap = dp is not None and getattr(dp, "overlap", True)
     if overlap:
         dp.arm(net, optimizer.flat)  # bucket all-reduces issued during the backward
-    loss = diffusion.loss(x0, cond, t=t, noise=noise)
+    comps = None
+    if not return_components:
+        loss = diffusion.loss(x0, cond, t=t, noise=noise, row0=row0)
+    elif diffusion.weighted:
+        c = diffusion.loss_components(x0, cond, t=t, noise=noise, row0=row0)
+        loss = c["total"]
+        comps = torch.stack([c["mse_raw"], c["mse_lat"], c["cond_loss"], loss.detach()])
+    else:
+        loss = diffusion.loss(x0, cond, t=t, noise=noise)
+        comps = torch.stack([loss.detach(), loss.detach(), torch.zeros_like(loss), loss.detach()])
     loss.backward()
     if overlap:
         dp.finish(net)
@@ -89,18 +117,22 @@ def train_step(diffusion, optimizer, x0, cond, max_grad_norm=1.0, dp=None, t=Non
         dp.allreduce_grads(optimizer.flat.grad)
     optimizer.max_grad_norm = max_grad_norm
     optimizer.step(loss=loss.detach())
-    return loss.detach()
+    return (loss.detach(), comps) if return_components else loss.detach()
 
 
 def train_one_epoch(diffusion, dl, optimizer, device, max_grad_norm=1.0, use_amp=True, epoch=1, dp=None, seed=None,
-                    ema=None):
+                    ema=None, metric_logger=None):
     """train.py:808-911; returns the epoch's mean loss.  With dp (world > 1) and no generator set yet, each rank
     draws t / eps from its own stream (dp_generator: base `seed`, or one broadcast from rank 0).
 
     ema (train.py:819): an ema.EMA attached to `optimizer`.  Its update happens inside optimizer.step(), in the AdamW
     launch and only for an applied step, so this loop has no `ema.update()` to call; the argument is checked, and
     ema_model follows use_amp.  Data-parallel runs need nothing more: after the gradient all-reduce every rank applies
-    the same step to the same weights, so the ranks' EMAs stay equal."""
+    the same step to the same weights, so the ranks' EMAs stay equal.
+
+    A weighted loss (diffusion.weighted) gets the crop row offsets of each batch from the loader's `last_row0`
+    (data.DeviceWindowLoader / PinnedWindowLoader; a loader without it: no crop).  metric_logger (train.py:83-96, :898):
+    its log(epoch, step, mse_raw, mse_lat, cond_loss, total) is called once per step with host floats."""
     if ema is not None and getattr(optimizer, "ema", None) is not ema:
         raise ValueError("ema is not attached to this optimizer (EMA(model, optimizer) attaches it; was it detached, "
                          "or built for another optimizer?)")
@@ -110,14 +142,24 @@ def train_one_epoch(diffusion, dl, optimizer, device, max_grad_norm=1.0, use_amp
         ema.ema_model.compute_dtype = diffusion.model.compute_dtype
     if dp is not None and getattr(dp, "world", 1) > 1 and diffusion.generator is None:
         diffusion.generator = dp_generator(device, dp, seed)
+    weighted = getattr(diffusion, "weighted", False)
     total, steps = 0.0, 0
     for step, (cond, x0) in enumerate(dl, start=1):
         cond = cond.to(device, non_blocking=True)
         x0 = x0.to(device, non_blocking=True)
-        loss = train_step(diffusion, optimizer, x0, cond, max_grad_norm, dp)
-        val = float(loss.item())
+        row0 = getattr(dl, "last_row0", None) if weighted else None  # the offsets of the batch just yielded
+        if metric_logger is None:
+            row = None
+            val = float(train_step(diffusion, optimizer, x0, cond, max_grad_norm, dp, row0=row0).item())
+        else:
+            _, comps = train_step(diffusion, optimizer, x0, cond, max_grad_norm, dp, row0=row0,
+                                  return_components=True)
+            row = comps.tolist()  # mse_raw, mse_lat, cond_loss, total: the step's one device-to-host copy
+            val = row[3]
         if not torch.isfinite(torch.tensor(val)):
             raise RuntimeError(f"Non-finite loss at epoch {epoch} step {step}: {val}")
+        if row is not None:
+            metric_logger.log(epoch, step, *row)
         total += val
         steps += 1
     return total / max(1, steps)

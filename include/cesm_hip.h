@@ -339,6 +339,23 @@ int cesm_ddim_step(const float* x, const float* eps, const float* z, const int64
 int cesm_mse(const float* pred, const float* tgt, float* loss, float* part, int64_t n, hipStream_t stream);
 int cesm_mse_bwd(const float* pred, const float* tgt, const float* gscale, float* dpred, int64_t n,
                  hipStream_t stream);
+/* Weighted loss: latitude (row) weights and per-sample weights on the one squared-error sum.  pred, noise: [B][V][H][W]
+ * fp32, d = pred - noise, n = B V H W; w: [Hg] fp32 row weights of the full grid, Hg >= H; row0: [B] int64, the grid
+ * row of each sample's row 0 (NULL: all 0); a: [B] fp32 per-sample weights (NULL: all 1); lam in [0, 1].
+ * With c(b, h) = (1 - lam) + lam w[row0[b] + h], formed once per row in fp32:
+ *   out[0] = mse_raw = (1/n) sum d^2,  out[1] = mse_lat = (1/n) sum w[row0[b] + h] d^2,
+ *   out[2] = total = (1/n) sum a[b] c(b, h) d^2;   cesm_wloss_bwd: dpred = gscale[0] (2/n) a[b] c(b, h) d.
+ * The row index row0[b] + h is clamped into [0, Hg - 1] before w is read: a wrong offset gives a wrong number, not a
+ * read outside w.  Deterministic: no atomics; part (512 * 3 floats) takes three fp32 partials per block, which a
+ * second kernel (one wave) adds in double in a fixed order.  Two launches forward, one backward.  16-byte accesses where
+ * W % 4 == 0 and pred, noise (and dpred) are 16-byte aligned, else one element per access.  CESM_EINVAL on a null
+ * pointer (row0 and a excepted), a size < 1, Hg < H or lam outside [0, 1].
+ * Added entry points (no existing argument list changed): the ABI version stays, as for cesm_stem_dgrad. */
+int cesm_wloss(const float* pred, const float* noise, const float* w, const int64_t* row0, const float* a, float lam,
+               float* out, float* part, int B, int V, int H, int W, int Hg, hipStream_t stream);
+int cesm_wloss_bwd(const float* pred, const float* noise, const float* w, const int64_t* row0, const float* a,
+                   float lam, const float* gscale, float* dpred, int B, int V, int H, int W, int Hg,
+                   hipStream_t stream);
 /* clip_grad_norm_ (train.py:865; torch/nn/utils/clip_grad.py:165-180) over a flat grad buffer;
  * info = {norm, clamped clip coef, finite(loss & norm)} stays on device (no host sync). */
 int cesm_grad_norm(const float* g, int64_t n, float max_norm, const float* loss, double* part, float* info,
