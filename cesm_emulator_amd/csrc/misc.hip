@@ -9,6 +9,7 @@
 #include "cesm_hip.h"
 #include "stem_dgrad.h"  // the stem's data gradient: kernels and launcher (cesm_stem_dgrad below)
 #include "multivar.h"    // stem and head for 2..4 target variables: kernels and launchers (cesm_*_mv below)
+#include "ensemble.h"    // ensemble verification statistics: kernels and launcher (cesm_ens_stats below)
 
 namespace {
 
@@ -701,6 +702,13 @@ int cesm_wloss_bwd(const float* pred, const float* noise, const float* w, const 
     wloss_bwd_kernel<false><<<g.grid, 256, 0, stream>>>(pred, noise, w, row0, a, lam, gscale, dpred, R, V, H, W, Hg,
                                                         g.L);
   return cesm_launch_status();
+}
+
+// ensemble mean / variance / fair CRPS / rank maps and their row-weighted sums (kernels: ensemble.h)
+int cesm_ens_stats(const float* ens, const float* obs, const float* w, const int64_t* row0, float* mean, float* var,
+                   float* crps, int* rank, double* acc, float* part, int B, int M, int V, int H, int W, int Hg,
+                   int accumulate, hipStream_t stream) {
+  return ens_stats_launch(ens, obs, w, row0, mean, var, crps, rank, acc, part, B, M, V, H, W, Hg, accumulate, stream);
 }
 
 // info[3] (device): norm, clip coef, finite flag.  part: 1024 doubles.

@@ -858,6 +858,76 @@ def wloss_bwd(pred, noise, w, row0, a, lam, gscale):
     return d
 
 
+ENS_MIN_M, ENS_MAX_M = 2, 128   # csrc/ensemble.h
+ENS_PART_BLOCKS = 2048           # block partials cesm_ens_stats may write (its `part` workspace)
+
+
+def ens_stats(ens, obs, w, row0=None, mean=True, var=True, crps=None, rank=None, acc=True, accumulate=False):
+    """Ensemble verification statistics (cesm_ens_stats; the per-pixel contract is in include/cesm_hip.h): one pass over
+    ens [B, M, V, H, W] fp32 (2 <= M <= 128; an [B * M, V, H, W] sampler batch viewed, member m of condition b = row
+    b M + m) against obs [B, V, H, W] or None, with row weights w [Hg] and crop row offsets row0 [B] int64 (None: 0; a
+    device tensor, not range-checked: the kernel clamps the row index into w).
+
+    mean / var / crps / rank select the maps ([B, V, H, W]; fp32, rank int32); crps and rank default to `obs is not
+    None` and need it.  acc: True allocates the float64 [V, 4 + M + 1] accumulator, False leaves it out, a tensor is
+    used as given (accumulate=True adds to it, else it is overwritten).  Row v of acc holds the sums, weighted with
+    w[row0[b] + h], of 1, (mean - obs)^2, var, crps and [rank = r] for r = 0 .. M; without obs only columns 0 and 2 are
+    written.  Returns {"mean", "var", "crps", "rank", "acc"} with None for what was left out."""
+    if not torch.is_tensor(ens) or ens.ndim != 5:
+        raise RuntimeError("shape mismatch: ens must be [B, M, V, H, W], got "
+                           f"{tuple(ens.shape) if torch.is_tensor(ens) else type(ens).__name__}")
+    B, M, V, H, W = ens.shape
+    if M < ENS_MIN_M:
+        raise ValueError(f"an ensemble needs at least {ENS_MIN_M} members (M - 1 divides the variance), got M = {M}")
+    if M > ENS_MAX_M:
+        raise NotImplementedError(f"cesm_ens_stats handles at most {ENS_MAX_M} members, got M = {M}")
+    if min(B, V, H, W) < 1:
+        raise RuntimeError(f"shape mismatch: empty ensemble {tuple(ens.shape)}")
+    crps = (obs is not None) if crps is None else bool(crps)
+    rank = (obs is not None) if rank is None else bool(rank)
+    if obs is None and (crps or rank):
+        raise ValueError("the crps and rank maps need obs")
+    if obs is not None and (not torch.is_tensor(obs) or tuple(obs.shape) != (B, V, H, W)):
+        raise RuntimeError(f"shape mismatch: obs must be {(B, V, H, W)}, got "
+                           f"{tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
+    if not torch.is_tensor(w) or w.ndim != 1 or w.numel() < H:
+        raise RuntimeError(f"shape mismatch: w must be [Hg] with Hg >= H = {H}")
+    if row0 is not None and (not torch.is_tensor(row0) or tuple(row0.shape) != (B,)):
+        raise RuntimeError(f"shape mismatch: row0 must be [{B}]")
+    own_acc = torch.is_tensor(acc)
+    if own_acc and tuple(acc.shape) != (V, 4 + M + 1):
+        raise RuntimeError(f"shape mismatch: acc must be {(V, 4 + M + 1)}, got {tuple(acc.shape)}")
+    want_acc = own_acc or bool(acc)
+    if not (mean or var or crps or rank or want_acc):
+        raise ValueError("ens_stats: no output selected")
+    _chk(ens, dtype=torch.float32)
+    _chk(obs, dtype=torch.float32)
+    _chk(w, dtype=torch.float32)
+    _chk(row0, dtype=torch.int64)
+    if own_acc:
+        _chk(acc, dtype=torch.float64)
+    for t in (obs, w, row0, acc if own_acc else None):
+        if t is not None and t.device != ens.device:
+            raise RuntimeError(f"tensors on different devices: {t.device} and {ens.device}")
+    dev = ens.device
+    out = {"mean": empty((B, V, H, W), torch.float32, dev) if mean else None,
+           "var": empty((B, V, H, W), torch.float32, dev) if var else None,
+           "crps": empty((B, V, H, W), torch.float32, dev) if crps else None,
+           "rank": empty((B, V, H, W), torch.int32, dev) if rank else None,
+           "acc": None}
+    part = None
+    if want_acc:
+        if not own_acc:
+            acc = empty((V, 4 + M + 1), torch.float64, dev)
+            if accumulate:
+                acc.zero_()
+        out["acc"] = acc
+        part = empty((ENS_PART_BLOCKS * (4 + M + 1),), torch.float32, dev)
+    call("cesm_ens_stats", P(ens), P(obs), P(w), P(row0), P(out["mean"]), P(out["var"]), P(out["crps"]),
+         P(out["rank"]), P(out["acc"]), P(part), B, M, V, H, W, w.numel(), int(bool(accumulate)), S())
+    return out
+
+
 def grad_norm(flat_grad, max_norm, loss=None):
     info = empty((4,), torch.float32, flat_grad.device)
     part = empty((1024,), torch.float64, flat_grad.device)

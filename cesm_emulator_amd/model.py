@@ -135,6 +135,25 @@ def min_snr_weights(alphas_cumprod, gamma):
     return (gamma * (1.0 - ac) / ac).clamp_max(1.0).float()
 
 
+def check_row0(row0, B, H, Hg, device, has_lat=True):
+    """Crop row offsets as a device int64 [B] tensor (None stays None): the check of Diffusion.loss_components and of
+    ensemble.ensemble_stats.  A list or CPU tensor is range-checked (0 <= row0, row0 + H <= Hg, else ValueError); a
+    device tensor is NOT read back (no synchronisation): the kernels clamp the row index, so a wrong device row0 gives
+    a wrong number, never a fault.  has_lat=False only words the error (no latitudes: the batch is the whole grid)."""
+    if row0 is None:
+        return None
+    if torch.is_tensor(row0) and row0.is_cuda:
+        return row0.to(device=device, dtype=torch.long).contiguous()
+    r = torch.as_tensor(row0, dtype=torch.long).reshape(-1)
+    if r.numel() != B:
+        raise ValueError(f"row0 needs one entry per sample ({B}), got {r.numel()}")
+    if bool(((r < 0) | (r + H > Hg)).any()):
+        hint = "" if has_lat else " (no `lat` given: the batch is the whole grid, so row0 must be 0)"
+        raise ValueError(f"row0 must satisfy 0 <= row0 and row0 + H <= Hg with H = {H}, Hg = {Hg}, got "
+                         f"{r.tolist()}{hint}")
+    return r.to(device)
+
+
 class Diffusion(nn.Module):
     """model.py:141-208 — linear β schedule (1e-4 → 2e-2), ε-prediction MSE.
 
@@ -233,18 +252,7 @@ class Diffusion(nn.Module):
         """row0 as a device int64 [B] tensor (None stays None).  A list or CPU tensor is range-checked here; a device
         tensor is NOT read back (no synchronisation): the kernel's clamp of the row index is its only guard, so a
         wrong device row0 gives a wrong loss, never a fault."""
-        if row0 is None:
-            return None
-        if torch.is_tensor(row0) and row0.is_cuda:
-            return row0.to(device=device, dtype=torch.long).contiguous()
-        r = torch.as_tensor(row0, dtype=torch.long).reshape(-1)
-        if r.numel() != B:
-            raise ValueError(f"row0 needs one entry per sample ({B}), got {r.numel()}")
-        if bool(((r < 0) | (r + H > Hg)).any()):
-            hint = " (no `lat` given: the batch is the whole grid, so row0 must be 0)" if self._lat is None else ""
-            raise ValueError(f"row0 must satisfy 0 <= row0 and row0 + H <= Hg with H = {H}, Hg = {Hg}, got "
-                             f"{r.tolist()}{hint}")
-        return r.to(device)
+        return check_row0(row0, B, H, Hg, device, has_lat=self._lat is not None)
 
     def loss_components(self, x0, cond, t=None, noise=None, row0=None):
         """The reference training loop's hook (train.py:836-841): {'mse_raw', 'mse_lat', 'cond_loss', 'total'} as 0-d
@@ -354,9 +362,75 @@ class Diffusion(nn.Module):
         [N, *shape] (entry k for executed step k, the last one unused).  ddim_eta = 0 with x_T draws nothing."""
         return self._sample(cond, shape, device, use_graph, x_T, noise_seq, steps, ddim_eta, False)
 
-    def _sample(self, cond, shape, device, use_graph, x_T, noise_seq, steps, ddim_eta, paired):
+    @torch.no_grad()
+    def sample_ensemble(self, cond, members, device=None, steps=None, ddim_eta=0.0, member_batch=None, x_T=None,
+                        noise_seq=None, use_graph=None):
+        """`members` samples for every row of cond: [B, M, V, H, W] fp32 (cond [B, V, H, W] or a window
+        [B, V, Fc, H, W]).  The B M jobs, b-major (job b M + m is member m of cond[b]), run in chunks of at most
+        member_batch network samples (default: all in one chunk); each chunk goes through sample()'s loop with
+        cond[b_idx] of its jobs and is written straight into its slice of the result, so no [M, B, ...] stack is built.
+        On the graph path one GraphSampleStep is captured per distinct chunk size of the call (at most two: the full
+        chunks and a shorter last one); later chunks of that size load their cond and x_T into its static buffers.
+
+        steps / ddim_eta / use_graph: as sample().  RNG use, chunk by chunk: randn for the chunk's x_T, then that
+        chunk's step noise exactly as sample() documents, then the next chunk.  Test hooks: x_T [B, M, V, H, W] and
+        noise_seq [N, B, M, V, H, W] replace the draws, sliced per chunk; with them a chunk equals, bit for bit,
+        sample(cond.repeat_interleave(M, 0)[chunk], ..., x_T=..., noise_seq=...) on the same rows."""
+        return self._sample_ensemble(cond, members, device, steps, ddim_eta, member_batch, x_T, noise_seq, use_graph,
+                                     False)
+
+    def _sample_ensemble(self, cond, members, device, steps, ddim_eta, member_batch, x_T, noise_seq, use_graph, paired):
+        """sample_ensemble(); paired: cond is two halves [cond, cond2] whose jobs b M + m get the same x_T and step
+        noise (one chunk only: counterfactual_delta)"""
+        if cond.ndim not in (4, 5):
+            raise ValueError(f"cond must be [B, V, H, W] or [B, V, Fc, H, W], got {tuple(cond.shape)}")
+        M = int(members)
+        if M < 1:
+            raise ValueError(f"members must be >= 1, got {members}")
+        device = cond.device if device is None else torch.device(device)
+        B, V, H, W = cond.shape[0], cond.shape[1], cond.shape[-2], cond.shape[-1]
+        jobs = B * M
+        mb = jobs if member_batch is None else int(member_batch)
+        if mb < 1:
+            raise ValueError(f"member_batch must be >= 1, got {member_batch}")
+        if paired and mb < jobs:
+            raise ValueError("paired ensembles run in one chunk")
+        if x_T is not None and tuple(x_T.shape) != (B, M, V, H, W):
+            raise ValueError(f"x_T must be {(B, M, V, H, W)}, got {tuple(x_T.shape)}")
+        if noise_seq is not None and tuple(noise_seq.shape[1:]) != (B, M, V, H, W):
+            raise ValueError(f"noise_seq must be [N, {B}, {M}, {V}, {H}, {W}], got {tuple(noise_seq.shape)}")
+        if use_graph is None:
+            use_graph = os.environ.get("CESM_SAMPLE_GRAPH", "1") != "0"
+        eta = None if steps is None else float(ddim_eta)
+        if steps is not None:
+            self.sample_schedule(steps)  # range check before anything is captured
+        with torch.inference_mode():
+            cond = cond.to(device)
+            out = torch.empty((B, M, V, H, W), dtype=torch.float32, device=device)
+            flat = out.view(jobs, V, H, W)
+            xT = None if x_T is None else x_T.reshape(jobs, V, H, W)
+            ns = None if noise_seq is None else noise_seq.reshape(noise_seq.shape[0], jobs, V, H, W)
+            captured = {}  # chunk size -> GraphSampleStep
+            for j0 in range(0, jobs, mb):
+                j1 = min(j0 + mb, jobs)
+                n = j1 - j0
+                c = cond[torch.arange(j0, j1, device=device) // M]
+                step = None
+                if use_graph:
+                    step = captured.get(n)
+                    if step is None:
+                        step = captured[n] = GraphSampleStep(self, c, torch.zeros((n, V, H, W), device=device),
+                                                             ddim_eta=eta)
+                x = self._sample(c, (n, V, H, W), device, use_graph, None if xT is None else xT[j0:j1],
+                                 None if ns is None else ns[:, j0:j1], steps, ddim_eta, paired, step=step)
+                flat[j0:j1].copy_(x)
+            return out
+
+    def _sample(self, cond, shape, device, use_graph, x_T, noise_seq, steps, ddim_eta, paired, step=None):
         """sample(); paired: the batch is two halves that get the same x_T and the same step noise (drawn for one
-        half, copied to the other: counterfactual_delta)"""
+        half, copied to the other: counterfactual_delta).  step: a GraphSampleStep captured earlier for this batch
+        size and ddim_eta (sample_ensemble); the graph path then loads cond and x_T into its static buffers instead of
+        capturing a new one, and the result is that step's x buffer (valid until the step runs again)."""
         if steps is not None:
             tau = self.sample_schedule(steps)
             ddim_eta = float(ddim_eta)
@@ -396,7 +470,10 @@ class Diffusion(nn.Module):
                             nz = noise_seq[k].to(device) if noise_seq is not None else randn()
                         x = self.ddim_step(x, cond, t_tensor, tp_tensor, ddim_eta, noise=nz)
                     return x
-                step = GraphSampleStep(self, cond, x, ddim_eta=ddim_eta)
+                if step is None:
+                    step = GraphSampleStep(self, cond, x, ddim_eta=ddim_eta)
+                else:
+                    step.load(cond, x)
                 for k, (tt, tp) in enumerate(pairs):
                     if noisy and tp >= 0:  # the last step's sigma is exactly 0: z stays as it is
                         if noise_seq is not None:
@@ -413,7 +490,10 @@ class Diffusion(nn.Module):
                         nz = randn()
                     x = self.p_sample(x, cond, t_tensor, noise=nz)
                 return x
-            step = GraphSampleStep(self, cond, x)
+            if step is None:
+                step = GraphSampleStep(self, cond, x)
+            else:
+                step.load(cond, x)
             for i, tt in enumerate(reversed(range(self.T))):
                 if tt == 0:
                     step.z.zero_()
@@ -456,6 +536,15 @@ class GraphSampleStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self._step()
+
+    def load(self, cond, x):
+        """copy a new cond and a new state x into the static buffers: the captured graph then steps them (shapes as at
+        capture)"""
+        if tuple(x.shape) != tuple(self.x.shape) or tuple(cond.shape) != tuple(self.cond.shape):
+            raise ValueError(f"GraphSampleStep captured for x {tuple(self.x.shape)} and cond {tuple(self.cond.shape)}, "
+                             f"got {tuple(x.shape)} and {tuple(cond.shape)}")
+        self.x.copy_(x)
+        self.cond.copy_(cond)
 
     def _step(self):
         eps = self.d.model(self.x, self.cond, self.t).float().contiguous()

@@ -11,11 +11,14 @@ Differences from the reference, all deliberate:
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from .model import UNet, Diffusion
 from .optim import FusedAdamW
 from .ema import EMA
+from .ensemble import EnsembleVerifier
 
 
 def build_model_from_config(cfg_unet):
@@ -163,3 +166,29 @@ def train_one_epoch(diffusion, dl, optimizer, device, max_grad_norm=1.0, use_amp
         total += val
         steps += 1
     return total / max(1, steps)
+
+
+def validate_ensemble(diffusion, loader, members, steps=None, ddim_eta=0.0, member_batch=None, max_batches=None,
+                      ema=None):
+    """Ensemble verification over a loader of (cond, target) batches: per batch, `members` samples per condition
+    (Diffusion.sample_ensemble with steps / ddim_eta / member_batch) are judged against the loader's target with the
+    batch's crop row offsets (`loader.last_row0`; a loader without it: no crop), all batches accumulated on the device
+    (ensemble.EnsembleVerifier, one kernel call per batch, no host synchronisation).  Returns the verifier's result():
+    per-variable mse, rmse, var, spread, ssr, crps and rank_hist, area-weighted with the diffusion's `lat` (uniform
+    weights without one).  ema: an ema.EMA; sampling then runs under ema.applied(diffusion).  max_batches: stop after
+    that many batches.  RNG use is sample_ensemble's, batch after batch."""
+    verifier = None
+    with (ema.applied(diffusion) if ema is not None else contextlib.nullcontext()):
+        for k, (cond, x0) in enumerate(loader):
+            if max_batches is not None and k >= max_batches:
+                break
+            row0 = getattr(loader, "last_row0", None)  # the offsets of the batch just yielded
+            device = next(diffusion.parameters()).device
+            cond, x0 = cond.to(device), x0.to(device).float().contiguous()
+            if verifier is None:
+                verifier = EnsembleVerifier(members, x0.shape[1], lat=diffusion._lat, device=device)
+            ens = diffusion.sample_ensemble(cond, members, steps=steps, ddim_eta=ddim_eta, member_batch=member_batch)
+            verifier.update(ens, x0, row0=row0)
+    if verifier is None:
+        raise ValueError("validate_ensemble: the loader gave no batch")
+    return verifier.result()

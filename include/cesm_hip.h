@@ -356,6 +356,29 @@ int cesm_wloss(const float* pred, const float* noise, const float* w, const int6
 int cesm_wloss_bwd(const float* pred, const float* noise, const float* w, const int64_t* row0, const float* a,
                    float lam, const float* gscale, float* dpred, int B, int V, int H, int W, int Hg,
                    hipStream_t stream);
+/* Ensemble verification statistics in one pass over the ensemble.  ens: [B][M][V][H][W] fp32, contiguous, member m of
+ * condition b = row b M + m of a sampler batch, 2 <= M <= 128; obs: [B][V][H][W] fp32 or NULL; w: [Hg] fp32 row weights,
+ * Hg >= H; row0: [B] int64 grid row of each condition's row 0 (NULL: all 0).  Per pixel, evaluated in fp32 in this form
+ * (the order of summation within a pixel is fixed but unspecified):
+ *   s = sum_m x_m,  mean = s / M;   q = sum_m (x_m - mean)^2,  var = q / (M - 1)   (two passes, never sum x^2 - s^2 / M)
+ *   A = sum_m |x_m - y|,  P = sum_{i<j} |x_i - x_j|,  crps = A / M - P / (M (M - 1))   (fair CRPS, Ferro 2014)
+ *   rank = #{m : x_m < y} in [0, M], ties count as not-less.
+ * Outputs, each nullable: maps mean, var, crps (fp32) and rank (int32), [B][V][H][W]; crps and rank need obs.  acc:
+ * double [V][4 + M + 1]; row v = sums over that variable's b, h, w, with w_r = w[clamp(row0[b] + h, 0, Hg - 1)], of
+ *   w_r,  w_r (mean - y)^2,  w_r var,  w_r crps,  w_r [rank = r] for r = 0 .. M;
+ * without obs only columns 0 and 2 are written, the rest of the row is left as found.  accumulate != 0: acc += the
+ * sums, else acc = the sums.  part: workspace of 2048 (4 + M + 1) floats, needed with acc.
+ * The row index is clamped before w is read: a wrong offset gives a wrong number, never a read outside w.
+ * Deterministic: no float atomics; per block fp32 partials in which a row's weight meets that row's sum once and rank
+ * counts are integers until then; the blocks' partials are added in double in a fixed order by a second kernel (one
+ * wave per accumulator entry).  ens is read once, 16 bytes per lane where W % 4 == 0 and ens is 16-byte aligned, else
+ * 4; any W.  P is formed pairwise from LDS (csrc/ensemble.h has the layout); M is a run-time value and nothing is
+ * padded.  Non-finite inputs may give non-finite outputs; rank stays in [0, M].
+ * CESM_EINVAL: ens or w null, M outside 2 .. 128, a size < 1, Hg < H, crps or rank without obs, acc without part, or
+ * no output at all.  An added entry point (no existing argument list changed): the ABI version stays. */
+int cesm_ens_stats(const float* ens, const float* obs, const float* w, const int64_t* row0, float* mean, float* var,
+                   float* crps, int* rank, double* acc, float* part, int B, int M, int V, int H, int W, int Hg,
+                   int accumulate, hipStream_t stream);
 /* clip_grad_norm_ (train.py:865; torch/nn/utils/clip_grad.py:165-180) over a flat grad buffer;
  * info = {norm, clamped clip coef, finite(loss & norm)} stays on device (no host sync). */
 int cesm_grad_norm(const float* g, int64_t n, float max_norm, const float* loss, double* part, float* info,

@@ -1,0 +1,260 @@
+"""cesm_ens_stats on the GPU (csrc/ensemble.h, kernels.ens_stats) against the float64 reference of
+tests/test_ensemble_host.py (ref64, written from the contract in include/cesm_hip.h).  Every tensor the wrapper
+allocates starts as NaN (the `poisoned` fixture; int32 maps as a negative pattern), so an element the kernel leaves out
+shows."""
+import pytest
+import torch
+
+from cesm_emulator_amd import kernels as K
+from test_ensemble_host import ref64
+
+pytestmark = pytest.mark.gpu
+
+RANK_POISON = -7
+
+
+@pytest.fixture(autouse=True)
+def poisoned(monkeypatch):
+    def empty(shape, dtype, device):
+        t = torch.empty(shape, dtype=dtype, device=device)
+        return t.fill_(float("nan")) if t.is_floating_point() else t.fill_(RANK_POISON)
+    monkeypatch.setattr(K, "empty", empty)
+
+
+def lead_view(host, lead, dev):
+    """device copy of `host` that starts `lead` floats past a 256-byte aligned address"""
+    buf = torch.zeros(host.numel() + lead, dtype=host.dtype, device=dev)
+    v = buf[lead:].view(host.shape)
+    v.copy_(host)
+    assert v.data_ptr() % 16 == (4 * lead) % 16 and v.is_contiguous()
+    return v
+
+
+def exact_case(shape, seed, Hg_extra=3):
+    """integer members and obs in [-8, 8], w multiples of 1/4 in [0, 2], random in-range row0"""
+    B, M, V, H, W = shape
+    g = torch.Generator().manual_seed(seed)
+    ens = torch.randint(-8, 9, shape, generator=g).float()
+    obs = torch.randint(-8, 9, (B, V, H, W), generator=g).float()
+    w = torch.randint(0, 9, (H + Hg_extra,), generator=g).float() / 4
+    row0 = torch.randint(0, Hg_extra + 1, (B,), generator=g)
+    return ens, obs, w, row0
+
+
+def rel_l2(got, want):
+    return float((got.double().cpu() - want).norm() / want.norm())
+
+
+# ------------------------------------------------------------------------------------------ 1: exact data
+EXACT_SHAPES = [(2, 2, 1, 4, 8), (3, 4, 2, 5, 7), (2, 8, 1, 8, 64), (1, 32, 1, 3, 1030), (2, 16, 2, 2, 33),
+                (2, 32, 1, 192, 288)]
+LEADS = {(2, 8, 1, 8, 64): (0, 1, 2)}  # 4 and 8 bytes off a 16-byte boundary: the scalar path with W % 4 == 0
+
+
+@pytest.fixture(scope="module")
+def exact_refs():
+    """the float64 reference of every exact case, computed once"""
+    out = {}
+    for shape in EXACT_SHAPES:
+        ens, obs, w, row0 = exact_case(shape, seed=sum(shape))
+        out[shape] = (ens, obs, w, row0, ref64(ens, obs, w, row0))
+    return out
+
+
+@pytest.mark.parametrize("shape", EXACT_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_exact_on_integer_data(dev, exact_refs, shape):
+    """Integers of magnitude <= 8 and M a power of two: s, A and P are whole numbers below 2^24 and every deviation
+    x - mean a multiple of 1 / M, so q M^2 is a whole number <= 256 M^3 <= 2^23: every per-pixel sum is exact in fp32
+    in any order.  mean and rank must then be the float64 values bit for bit, var one rounding away (the division),
+    crps at most four roundings (A / M, P / (M (M - 1)), their difference).  Weights in quarters: sum w and the
+    histogram are exact in the block partials (multiples of 1/4 far below 2^24) and in the double sum."""
+    B, M, V, H, W = shape
+    ens, obs, w, row0, ref = exact_refs[shape]
+    assert M & (M - 1) == 0 and 256 * M ** 3 <= 2 ** 23
+    for k, scale in (("s", 1), ("q", M * M), ("A", 1), ("P", 1)):
+        v = ref[k] * scale
+        assert bool((v == v.round()).all()) and float(v.abs().max()) < 2 ** 24, k
+    for lead in LEADS.get(shape, (0,)):
+        r = K.ens_stats(lead_view(ens, lead, dev), obs.to(dev), w.to(dev), row0.to(dev))
+        assert torch.equal(r["mean"].cpu().double(), ref["mean"]), "mean not exact"
+        assert r["rank"].dtype == torch.int32 and torch.equal(r["rank"].cpu().long(), ref["rank"]), "rank"
+        verr = (r["var"].cpu().double() - ref["var"]).abs()
+        assert bool((verr <= 2.0 ** -22 * ref["var"]).all()), float((verr / ref["var"]).nan_to_num().max())
+        cerr = (r["crps"].cpu().double() - ref["crps"]).abs()
+        cbound = 2.0 ** -22 * (ref["A"] / M + ref["P"] / (M * (M - 1)))
+        assert bool((cerr <= cbound).all()), float((cerr - cbound).max())
+        acc = r["acc"].cpu()
+        assert acc.dtype == torch.float64 and tuple(acc.shape) == (V, 4 + M + 1)
+        assert torch.equal(acc[:, 0], ref["acc"][:, 0]), "sum w"
+        assert torch.equal(acc[:, 4:], ref["acc"][:, 4:]), "rank histogram"
+        rel = ((acc[:, 1:4] - ref["acc"][:, 1:4]).abs() / ref["acc"][:, 1:4].abs())
+        print(f"{shape} lead {lead}: worst accumulator column 1-3 rel {float(rel.max()):.2e}")
+        assert float(rel.max()) <= 1e-5
+        assert float(ref["acc"][:, 4:].sum()) == float(ref["acc"][:, 0].sum())  # every pixel has one rank
+
+
+# ------------------------------------------------------------------------------------------ 2: general M
+@pytest.mark.parametrize("M", [3, 5, 40, 100, 128])
+@pytest.mark.parametrize("bvhw", [(2, 1, 8, 64), (1, 2, 5, 7)], ids=["vector", "scalar"])
+def test_general_member_counts_on_normal_data(dev, M, bvhw):
+    """N(0, 1) members and obs, any M: every fp32 map within 1e-5 relative L2 of float64; rank equal except where the
+    comparison itself is within rounding (|x_m - y| < 2^-20 for some m), which continuous data does not produce."""
+    B, V, H, W = bvhw
+    g = torch.Generator().manual_seed(100 * M + W)
+    ens = torch.randn(B, M, V, H, W, generator=g)
+    obs = torch.randn(B, V, H, W, generator=g)
+    w = 2 * torch.rand(H + 2, generator=g)
+    row0 = torch.randint(0, 3, (B,), generator=g)
+    ref = ref64(ens, obs, w, row0)
+    near = ((ens.double() - obs.double()[:, None]).abs() < 2.0 ** -20).any(dim=1)
+    assert float(near.double().mean()) < 1e-3  # on the reference alone
+    r = K.ens_stats(ens.to(dev), obs.to(dev), w.to(dev), row0.to(dev))
+    for k in ("mean", "var", "crps"):
+        e = rel_l2(r[k], ref[k])
+        print(f"M={M} {bvhw} {k}: rel L2 {e:.2e}")
+        assert e <= 1e-5, k
+    assert torch.equal(r["rank"].cpu().long()[~near], ref["rank"][~near])
+    assert 0 <= int(r["rank"].min()) and int(r["rank"].max()) <= M
+    acc = r["acc"].cpu()
+    rel = (acc - ref["acc"]).abs() / ref["acc"].abs().clamp_min(1e-300)
+    assert float(rel[:, :4].max()) <= 1e-5
+    if not bool(near.any()):
+        assert float((acc[:, 4:] - ref["acc"][:, 4:]).abs().max()) <= 1e-5 * float(ref["acc"][:, 0].max())
+
+
+# ------------------------------------------------------------------------------------------ 3: offset data
+# measured worst relative L2 against float64 on the same fp32 inputs (MI355X; M = 40: var 5.7e-8, crps 5.4e-8;
+# M = 128: var 6.8e-8, crps 5.1e-8; the one-pass fp32 variance on the same data: 4.1e-2); the gate is twice the worst,
+# and never looser than 1e-4
+OFFSET_MEASURED = {"var": 6.8e-8, "crps": 5.4e-8}
+OFFSET_GATE = {k: min(2 * v, 1e-4) for k, v in OFFSET_MEASURED.items()}
+
+
+@pytest.mark.parametrize("shape", [(2, 40, 1, 8, 64), (1, 128, 2, 5, 7)], ids=["M40", "M128"])
+def test_offset_data_keeps_its_precision(dev, shape):
+    """x ~ N(288, 0.5^2), un-standardised kelvin: the spread is 1/600 of the values.  A one-pass variance
+    (sum x^2 - s^2 / M) loses log2(288^2 / 0.25) = 18 of fp32's 24 bits here; the two-pass form does not, and |x_i - x_j|
+    of neighbouring floats is exact."""
+    B, M, V, H, W = shape
+    g = torch.Generator().manual_seed(M)
+    ens = 288.0 + 0.5 * torch.randn(shape, generator=g)
+    obs = 288.0 + 0.5 * torch.randn(B, V, H, W, generator=g)
+    w = torch.ones(H)
+    ref = ref64(ens, obs, w)
+    r = K.ens_stats(ens.to(dev), obs.to(dev), w.to(dev))
+    one_pass = ((ens ** 2).sum(1) - ens.sum(1) ** 2 / M) / (M - 1)  # what the contract forbids, in fp32
+    print(f"{shape}: one-pass fp32 variance rel L2 {rel_l2(one_pass, ref['var']):.2e}")
+    for k in ("var", "crps"):
+        e = rel_l2(r[k], ref[k])
+        print(f"{shape} {k}: rel L2 {e:.3e} (gate {OFFSET_GATE[k]:.1e})")
+        assert e <= OFFSET_GATE[k], k
+    assert rel_l2(r["mean"], ref["mean"]) <= 1e-6
+
+
+# ------------------------------------------------------------------------------------------ 4: null arguments
+@pytest.mark.parametrize("shape", [(2, 8, 1, 8, 64), (3, 4, 2, 5, 7)], ids=["vector", "scalar"])
+def test_null_combinations(dev, shape):
+    B, M, V, H, W = shape
+    ens, obs, w, row0 = exact_case(shape, seed=11)
+    ref = ref64(ens, obs, w, row0)
+    e, o, wd, r0 = ens.to(dev), obs.to(dev), w.to(dev), row0.to(dev)
+    full = K.ens_stats(e, o, wd, r0)
+    # no obs: mean, var, columns 0 and 2; the rest of the accumulator stays as found (here: the poison)
+    r = K.ens_stats(e, None, wd, r0)
+    assert r["crps"] is None and r["rank"] is None
+    assert torch.equal(r["mean"], full["mean"]) and torch.equal(r["var"], full["var"])
+    acc = r["acc"].cpu()
+    assert torch.equal(acc[:, 0], ref["acc"][:, 0]) and torch.equal(acc[:, 2], full["acc"][:, 2].cpu())
+    assert bool(torch.isnan(acc[:, 1]).all() and torch.isnan(acc[:, 3:]).all())
+    # no maps
+    r = K.ens_stats(e, o, wd, r0, mean=False, var=False, crps=False, rank=False)
+    assert all(r[k] is None for k in ("mean", "var", "crps", "rank")) and torch.equal(r["acc"], full["acc"])
+    # no accumulator
+    r = K.ens_stats(e, o, wd, r0, acc=False)
+    assert r["acc"] is None and all(torch.equal(r[k], full[k]) for k in ("mean", "var", "crps", "rank"))
+    # single maps
+    r = K.ens_stats(e, o, wd, r0, mean=False, var=False, crps=True, rank=False, acc=False)
+    assert torch.equal(r["crps"], full["crps"]) and r["mean"] is None and r["rank"] is None
+    # row0 null equals zeros, and differs from the offsets
+    zeros = torch.zeros(B, dtype=torch.int64, device=dev)
+    assert torch.equal(K.ens_stats(e, o, wd, None)["acc"], K.ens_stats(e, o, wd, zeros)["acc"])
+    r0b = torch.tensor([3, 0, 1][:B], device=dev)
+    assert not torch.equal(K.ens_stats(e, o, wd, None)["acc"], K.ens_stats(e, o, wd, r0b)["acc"])
+
+
+def test_accumulate_adds_batches(dev):
+    """two halves of a batch accumulated = one call: sum w and the histogram exactly (integer data, quarter weights),
+    the other columns within 1e-12 relative (the same fp32 block partials may meet in another double order)"""
+    shape = (4, 8, 2, 6, 40)
+    ens, obs, w, row0 = exact_case(shape, seed=5)
+    e, o, wd, r0 = ens.to(dev), obs.to(dev), w.to(dev), row0.to(dev)
+    one = K.ens_stats(e, o, wd, r0, mean=False, var=False, crps=False, rank=False)["acc"]
+    acc = torch.zeros_like(one)
+    for sl in (slice(0, 2), slice(2, 4)):
+        got = K.ens_stats(e[sl].contiguous(), o[sl].contiguous(), wd, r0[sl].contiguous(), mean=False, var=False,
+                          crps=False, rank=False, acc=acc, accumulate=True)["acc"]
+        assert got is acc
+    assert torch.equal(acc[:, 0], one[:, 0]) and torch.equal(acc[:, 4:], one[:, 4:])
+    assert float(((acc - one).abs() / one.abs().clamp_min(1e-300)).max()) <= 1e-12
+    # accumulate=False overwrites; a fresh accumulator with accumulate=True starts from zero
+    K.ens_stats(e, o, wd, r0, mean=False, var=False, crps=False, rank=False, acc=acc, accumulate=False)
+    assert torch.equal(acc, one)
+    fresh = K.ens_stats(e, o, wd, r0, mean=False, var=False, crps=False, rank=False, accumulate=True)["acc"]
+    assert torch.equal(fresh, one)
+
+
+def test_two_launches_give_identical_bits(dev):
+    shape = (2, 40, 1, 24, 288)
+    g = torch.Generator().manual_seed(9)
+    ens = torch.randn(shape, generator=g).to(dev)
+    obs = torch.randn(2, 1, 24, 288, generator=g).to(dev)
+    w = (2 * torch.rand(24, generator=g)).to(dev)
+    a = K.ens_stats(ens, obs, w)
+    torch.empty(1 << 22, device=dev).normal_()  # other work in between
+    b = K.ens_stats(ens, obs, w)
+    for k in ("mean", "var", "crps", "rank", "acc"):
+        assert torch.equal(a[k], b[k]), k
+
+
+def test_far_row_offsets_and_extremes(dev):
+    shape = (2, 5, 1, 4, 12)
+    g = torch.Generator().manual_seed(2)
+    ens = torch.randn(shape, generator=g).to(dev)
+    obs = torch.randn(2, 1, 4, 12, generator=g).to(dev)
+    w = (1 + torch.rand(6, generator=g)).to(dev)
+    far = torch.tensor([10 ** 12, -10 ** 12], dtype=torch.int64, device=dev)
+    r = K.ens_stats(ens, obs, w, far)
+    assert all(bool(torch.isfinite(r[k]).all()) for k in ("mean", "var", "crps", "acc"))
+    # the clamp: sample 0 weighs w[-1] everywhere, sample 1 w[0]
+    assert abs(float(r["acc"][0, 0]) - 48 * (float(w[-1]) + float(w[0]))) <= 1e-4
+    M = shape[1]
+    hi = K.ens_stats(ens, torch.full_like(obs, 100.0), w)
+    lo = K.ens_stats(ens, torch.full_like(obs, -100.0), w)
+    assert bool((hi["rank"] == M).all()) and bool((lo["rank"] == 0).all())
+    sw = float(hi["acc"][0, 0])
+    assert float(hi["acc"][0, 4 + M]) == sw and float(hi["acc"][0, 4:4 + M].abs().sum()) == 0.0
+    assert float(lo["acc"][0, 4]) == sw and float(lo["acc"][0, 5:].abs().sum()) == 0.0
+    # non-finite members: no fault, ranks stay in range
+    bad = ens.clone()
+    bad[0, 1, 0, 0, 0] = float("nan")
+    bad[1, 2, 0, 1, 3] = float("inf")
+    r = K.ens_stats(bad, obs, w)
+    torch.cuda.synchronize()
+    assert 0 <= int(r["rank"].min()) and int(r["rank"].max()) <= M
+    assert bool(torch.isfinite(r["mean"][0, 0, 1]).all())
+
+
+def test_wrapper_refuses_bad_arguments_on_the_device(dev):
+    ens, obs, w = torch.zeros(2, 3, 1, 4, 8, device=dev), torch.zeros(2, 1, 4, 8, device=dev), torch.ones(4, device=dev)
+    with pytest.raises(RuntimeError, match="contiguous"):
+        K.ens_stats(ens.transpose(3, 4), obs.transpose(2, 3), torch.ones(8, device=dev))
+    with pytest.raises(RuntimeError, match="dtype"):
+        K.ens_stats(ens.double(), obs, w)
+    with pytest.raises(RuntimeError, match="dtype"):
+        K.ens_stats(ens, obs, w, torch.zeros(2, dtype=torch.int32, device=dev))
+    with pytest.raises(RuntimeError, match="device"):
+        K.ens_stats(ens, obs, w.cpu())
+    with pytest.raises(ValueError, match="at least 2"):
+        K.ens_stats(ens[:, :1].contiguous(), obs, w)
+    with pytest.raises(NotImplementedError, match="128"):
+        K.ens_stats(torch.zeros(1, 129, 1, 4, 8, device=dev), obs[:1], w)
