@@ -1,4 +1,4 @@
-// Weight gradients of the implicit-GEMM convolutions of conv.hip (geometry: ConvGeom, conv_common.h), the column sums
+// Weight gradients of the implicit-GEMM convolutions of conv_fwd.hip (geometry: ConvGeom, conv_common.h), the column sums
 // that give bias gradients, wgrad_plan and the cesm_conv_wgrad* / cesm_colsum ABI.
 //
 // Weight gradients use a second MFMA kernel (pixel axis = MFMA K) that writes fp32 split-K

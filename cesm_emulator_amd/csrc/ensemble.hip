@@ -3,8 +3,7 @@
 //   s = sum x_m, mean = s / M;  q = sum (x_m - mean)^2, var = q / (M - 1)   (two passes over the staged members)
 //   A = sum |x_m - y|,  P = sum_{i<j} |x_i - x_j|,  crps = A / M - P / (M (M - 1))   (fair CRPS, Ferro 2014)
 //   rank = #{m : x_m < y}
-// and per variable the row-weighted sums of (mean - y)^2, var, crps and of the rank histogram.  Included by misc.hip
-// (the set of compiled sources is fixed); kernels and launcher only, the extern "C" entry point is in misc.hip.
+// and per variable the row-weighted sums of (mean - y)^2, var, crps and of the rank histogram.
 //
 // Layout.  The unit of work is a chunk: PXB (32 or 64) consecutive pixels of one (b, v, h) row.  A 256-thread block
 // stages the chunk's M x PXB member values in LDS with one pass of coalesced loads (16 bytes per lane where W % 4 == 0
@@ -24,7 +23,10 @@
 // row weight once; the rank counts of a chunk are integers (LDS integer adds) before the weight touches them.  The
 // block partials part[v][blk][4 + M + 1] are added over blocks in double, in a fixed order, by ens_final_kernel.  No
 // float atomics anywhere.
-#pragma once
+#include <algorithm>
+
+#include "common.h"
+#include "cesm_hip.h"
 
 namespace {
 
@@ -261,3 +263,10 @@ int ens_stats_launch(const float* ens, const float* obs, const float* w, const i
 }
 
 }  // namespace
+
+// ensemble mean / variance / fair CRPS / rank maps and their row-weighted sums
+extern "C" int cesm_ens_stats(const float* ens, const float* obs, const float* w, const int64_t* row0, float* mean,
+                              float* var, float* crps, int* rank, double* acc, float* part, int B, int M, int V, int H,
+                              int W, int Hg, int accumulate, hipStream_t stream) {
+  return ens_stats_launch(ens, obs, w, row0, mean, var, crps, rank, acc, part, B, M, V, H, W, Hg, accumulate, stream);
+}

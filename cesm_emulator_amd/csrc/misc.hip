@@ -7,9 +7,6 @@
 //  * dtype casts and the training-window gather (dataset_single_member.py:168-196)
 #include "common.h"
 #include "cesm_hip.h"
-#include "stem_dgrad.h"  // the stem's data gradient: kernels and launcher (cesm_stem_dgrad below)
-#include "multivar.h"    // stem and head for 2..4 target variables: kernels and launchers (cesm_*_mv below)
-#include "ensemble.h"    // ensemble verification statistics: kernels and launcher (cesm_ens_stats below)
 
 namespace {
 
@@ -704,13 +701,6 @@ int cesm_wloss_bwd(const float* pred, const float* noise, const float* w, const 
   return cesm_launch_status();
 }
 
-// ensemble mean / variance / fair CRPS / rank maps and their row-weighted sums (kernels: ensemble.h)
-int cesm_ens_stats(const float* ens, const float* obs, const float* w, const int64_t* row0, float* mean, float* var,
-                   float* crps, int* rank, double* acc, float* part, int B, int M, int V, int H, int W, int Hg,
-                   int accumulate, hipStream_t stream) {
-  return ens_stats_launch(ens, obs, w, row0, mean, var, crps, rank, acc, part, B, M, V, H, W, Hg, accumulate, stream);
-}
-
 // info[3] (device): norm, clip coef, finite flag.  part: 1024 doubles.
 int cesm_grad_norm(const float* g, int64_t n, float max_norm, const float* loss, double* part, float* info,
                    hipStream_t stream) {
@@ -769,35 +759,6 @@ int cesm_cast(int dtype_in, int dtype_out, const void* x, void* y, int64_t n, hi
   else
     return CESM_EINVAL;
   return cesm_launch_status();
-}
-
-// stem data gradient (input gradients; kernels: stem_dgrad.h)
-int cesm_stem_dgrad(int dtype, const void* dy, const float* w, float* dxt, float* dcond, int B, int F, int Fx, int Fc,
-                    int H, int W, int Co, int KS, hipStream_t stream) {
-  return stem_dgrad_launch(dtype, dy, w, dxt, dcond, B, F, Fx, Fc, H, W, Co, KS, stream);
-}
-
-// stem and head for V target variables (kernels and launchers: multivar.h; V == 1 runs the entry points above)
-int cesm_stem_fwd_mv(int dtype, const float* xt, const float* cond, const float* w, const float* bias, void* y, int B,
-                     int V, int F, int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream) {
-  return mv_stem_fwd_launch(dtype, xt, cond, w, bias, y, B, V, F, Fx, Fc, H, W, Co, KS, stream);
-}
-int cesm_stem_wgrad_mv(int dtype, const float* xt, const float* cond, const void* dy, float* dw, float* part, int nblk,
-                       int B, int V, int F, int Fx, int Fc, int H, int W, int Co, int KS, int accumulate,
-                       hipStream_t stream) {
-  return mv_stem_wgrad_launch(dtype, xt, cond, dy, dw, part, nblk, B, V, F, Fx, Fc, H, W, Co, KS, accumulate, stream);
-}
-int cesm_stem_dgrad_mv(int dtype, const void* dy, const float* w, float* dxt, float* dcond, int B, int V, int F, int Fx,
-                       int Fc, int H, int W, int Co, int KS, hipStream_t stream) {
-  return mv_stem_dgrad_launch(dtype, dy, w, dxt, dcond, B, V, F, Fx, Fc, H, W, Co, KS, stream);
-}
-int cesm_head_fwd_mv(int dtype, const void* x, const float* w, const float* bias, float* out, int B, int V, int F,
-                     int HW, int C, hipStream_t stream) {
-  return mv_head_fwd_launch(dtype, x, w, bias, out, B, V, F, HW, C, stream);
-}
-int cesm_head_bwd_mv(int dtype, const float* dout, const void* x, const float* w, void* dx, float* dw, float* db,
-                     float* part, int nblk, int B, int V, int F, int HW, int C, int accumulate, hipStream_t stream) {
-  return mv_head_bwd_launch(dtype, dout, x, w, dx, dw, db, part, nblk, B, V, F, HW, C, accumulate, stream);
 }
 
 int cesm_window_gather(const float* cond, const float* tgt, const int64_t* items, float* cwin, float* x0,

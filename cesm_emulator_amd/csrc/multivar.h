@@ -3,8 +3,9 @@
 //         xt [B][V][Fx][H][W], cond [B][V][Fc][H][W] fp32 (Fx, Fc = 1 or F; 1 < F is a stride-0 read of frame 0),
 //         w [Co][2V][KS][KS] fp32, y / dy [B*F][H][W][Co] in the compute dtype
 //   head  Conv3d(C -> V, 1) on frame F/2: out [B][V][HW] fp32, w [V][C], bias [V]
-// V = 1 is not handled here: the *_mv entry points hand it to the single-variable entry points (conv.hip, misc.hip),
-// which launch what they always launched.  Everything is deterministic: no atomics, fixed summation orders.
+// V = 1 is not handled here: the *_mv entry points hand it to the single-variable entry points (stem_head.hip), which
+// launch what they always launched.  Everything is deterministic: no atomics, fixed summation orders.
+// Included by stem_head.hip alone, after its sum_partials_kernel, which the weight gradient's launcher here uses.
 #pragma once
 #include <algorithm>
 
@@ -395,26 +396,6 @@ __global__ __launch_bounds__(256) void mv_stem_wgrad_mfma_kernel(const float* __
     }
 }
 
-// dst[e] (+)= sum_k part[k][e]: 64 elements x 16 split groups per block, the 16 group sums added in a fixed order
-// (conv.hip's sum_partials_kernel; kernels are local to their source file)
-__global__ __launch_bounds__(1024) void mv_sum_partials_kernel(const float* __restrict__ part, float* __restrict__ dst,
-                                                               int nsplit, int64_t n, int accumulate) {
-  __shared__ float red[16][65];
-  const int el = threadIdx.x & 63, kg = threadIdx.x >> 6;
-  const int64_t e = blockIdx.x * (int64_t)64 + el;
-  float s = 0.f;
-  if (e < n)
-    for (int k = kg; k < nsplit; k += 16) s += part[(int64_t)k * n + e];
-  red[kg][el] = s;
-  __syncthreads();
-  if (kg == 0 && e < n) {
-    float t = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) t += red[q][el];
-    dst[e] = accumulate ? dst[e] + t : t;
-  }
-}
-
 // ---------------------------------------------------------------------------------------- stem data gradient
 //   dX_ci[b][f'][y][x] = sum_{f -> f'} sum_{co,ky,kx} w[co][ci][ky][kx] * dy[b,f][y - ky + P][x - kx + P][co]
 // dxt [B][V][Fx][H][W] (ci < V) and dcond [B][V][Fc][H][W] (ci >= V), each nullable.  The rules of stem_dgrad.h: a
@@ -736,7 +717,7 @@ int mv_head_bwd_t(const float* dout, const T* x, const float* w, T* dx, float* d
 
 }  // namespace
 
-// host launchers of the cesm_*_mv entry points (the ABI entries are in misc.hip)
+// host launchers of the cesm_*_mv entry points (the ABI entries are in stem_head.hip)
 static inline int mv_stem_fwd_launch(int dtype, const float* xt, const float* cond, const float* w, const float* bias, void* y, int B,
                      int V, int F, int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream) {
   if (V == 1) return cesm_stem_fwd(dtype, xt, cond, w, bias, y, B, F, Fx, Fc, H, W, Co, KS, stream);
@@ -788,7 +769,7 @@ static inline int mv_stem_wgrad_launch(int dtype, const float* xt, const float* 
                                                    (int)nt);
   }
   const int64_t n = (int64_t)Co * 2 * V * KS * KS;
-  mv_sum_partials_kernel<<<(unsigned)cdiv(n, 64), 1024, 0, stream>>>(part, dw, nblk, n, accumulate);
+  sum_partials_kernel<<<(unsigned)cdiv(n, 64), 1024, 0, stream>>>(part, dw, nblk, n, accumulate);
   return cesm_launch_status();
 }
 

@@ -1,5 +1,6 @@
 // Data gradient of the stem: the adjoint of Conv3d(2 -> Co, (1,KS,KS), pad KS/2) on cat([x_t, cond]) (the forward:
-// stem_fwd_kernel, conv.hip), for input gradients (saliency, guidance).  Off the training path.
+// stem_fwd_kernel, stem_head.hip, which includes this header), for input gradients (saliency, guidance).  Off the
+// training path.
 //
 //   dX_ci[b][f'][y][x] = sum_{f -> f'} sum_{co,ky,kx} w[co][ci][ky][kx] * dy[b,f][y - ky + P][x - kx + P][co]
 //
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(256) void stem_dgrad_mfma_kernel(const bf16* __rest
 
 }  // namespace
 
-// host launcher of cesm_stem_dgrad (the ABI entry is in misc.hip)
+// host launcher of cesm_stem_dgrad (the ABI entry is in stem_head.hip)
 static inline int stem_dgrad_launch(int dtype, const void* dy, const float* w, float* dxt, float* dcond, int B, int F,
                                     int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream) {
   if (dtype != CESM_DT_F32 && dtype != CESM_DT_BF16) return CESM_EINVAL;

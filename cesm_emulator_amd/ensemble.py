@@ -2,7 +2,7 @@
 
 The model emulates a large ensemble; Diffusion.sample_ensemble draws M members per condition.  This module judges
 them with the standard measures, all from ONE kernel pass over the [B, M, V, H, W] ensemble (kernels.ens_stats,
-csrc/ensemble.h; the per-pixel contract is in include/cesm_hip.h):
+csrc/ensemble.hip; the per-pixel contract is in include/cesm_hip.h):
 
   mse / rmse   of the ensemble mean against obs,            var / spread = sqrt(var)   mean ensemble variance,
   ssr          spread / skill = sqrt((M + 1) / M * var / mse)   (1 for a reliable ensemble; Fortin et al. 2014),

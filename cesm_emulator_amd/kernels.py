@@ -65,7 +65,7 @@ def conv_pack_into(w, out, cout, cin, kh, kw, swap, flip):
 
 
 def pack_blocks(cout, cin, kh, kw):
-    """blocks cesm_conv_pack_batch gives one job (host-only query; the kernel's own tiling, csrc/conv.hip)"""
+    """blocks cesm_conv_pack_batch gives one job (host-only query; the kernel's own tiling, csrc/conv_pack.hip)"""
     n = lib().cesm_conv_pack_blocks(int(cout), int(cin), int(kh), int(kw))
     if n < 0:
         raise ValueError(f"conv pack job {cout} x {cin} x {kh} x {kw}: more than 64 taps (or an empty weight) does not "
@@ -293,7 +293,7 @@ def stem_wgrad(xt, cond, dy, dw, F, accumulate=True):
 
 
 def stem_dgrad(dy, w, B, F, Fx, Fc, want_xt=True, want_cond=True):
-    """data gradient of the stem (csrc/stem_dgrad.h, csrc/multivar.h): dy [B*F, H, W, Co] (the tensor stem_wgrad reads),
+    """data gradient of the stem (csrc/stem_head.hip: stem_dgrad.h, multivar.h): dy [B*F, H, W, Co] (what stem_wgrad reads),
     w the fp32 stem weight [Co, 2V, 1, KS, KS].  Returns (dxt [B, V, Fx, H, W], dcond [B, V, Fc, H, W]) fp32 ([B, Fx, H,
     W] and [B, Fc, H, W] at V = 1), None where not wanted; an input that was broadcast over frames (Fx or Fc == 1 < F)
     gets the sum over the F frames."""
@@ -858,7 +858,7 @@ def wloss_bwd(pred, noise, w, row0, a, lam, gscale):
     return d
 
 
-ENS_MIN_M, ENS_MAX_M = 2, 128   # csrc/ensemble.h
+ENS_MIN_M, ENS_MAX_M = 2, 128   # csrc/ensemble.hip
 ENS_PART_BLOCKS = 2048           # block partials cesm_ens_stats may write (its `part` workspace)
 
 

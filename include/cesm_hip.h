@@ -46,7 +46,7 @@ int cesm_abi_version(void);
  * distributed.XgmiModelReducer). */
 int cesm_hold_cus(int nblk, float usec, hipStream_t stream);
 
-/* ---- convolutions (csrc/conv.hip, conv_wgrad.hip) -------------------------------------
+/* ---- convolutions (csrc/conv_fwd.hip with conv_halo.hip and conv_level0.hip; conv_wgrad.hip; conv_pack.hip) ------
  * Generic implicit-GEMM conv on MFMA. Replaces nn.Conv3d (1,k,k) at video_net.py:215 (Block.proj),
  * :246 (res_conv), :61-62 (Downsample), nn.ConvTranspose3d at :65-66 (Upsample), the attention
  * projections nn.Linear :380-381 and 1x1 nn.Conv2d :322-323, and all their data gradients.
@@ -113,7 +113,8 @@ int cesm_conv_pack_batch(int dtype, const int64_t* jobs, int njobs, int nblocks,
 /* dst[c] (+)= sum over rows of x[r][c]  (conv bias gradients) ; part: nsplit*C floats */
 int cesm_colsum(int dtype, const void* x, float* dst, float* part, int nsplit, int64_t rows, int C, int accumulate,
                 hipStream_t stream);
-/* stem Conv3d(2->Co,(1,KS,KS),pad KS/2) on cat([x_t, cond]) read straight from the NCDHW fp32 boundary
+/* ---- stem and head (csrc/stem_head.hip with stem_dgrad.h and multivar.h) --------------------------
+ * stem Conv3d(2->Co,(1,KS,KS),pad KS/2) on cat([x_t, cond]) read straight from the NCDHW fp32 boundary
  * tensors (video_net.py:595-600, :808-815; model.py:111-121 frame broadcast). */
 int cesm_stem_fwd(int dtype, const float* xt, const float* cond, const float* w, const float* bias, void* y, int B,
                   int F, int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream);
@@ -132,7 +133,7 @@ int cesm_head_fwd(int dtype, const void* x, const float* w, const float* bias, f
                   hipStream_t stream);
 int cesm_head_bwd(int dtype, const float* dout, const void* x, const float* w, void* dx, float* dw, float* db,
                   float* part, int nblk, int B, int F, int HW, int C, int accumulate, hipStream_t stream);
-/* The stem and head for V target variables, 1 <= V <= 4 (csrc/multivar.hip).  Tensors are the reference's:
+/* The stem and head for V target variables, 1 <= V <= 4 (csrc/multivar.h).  Tensors are the reference's:
  * xt [B][V][Fx][H][W], cond [B][V][Fc][H][W], stem w [Co][2V][KS][KS] with input channels 0..V-1 = x_t and V..2V-1 =
  * cond, dw the same shape, part nblk*Co*2V*KS*KS floats, dxt / dcond shaped like xt / cond (each nullable); head w
  * [V][C], bias / db [V], out / dout [B][V][HW], dw [V][C], part nblk*V*(C+1) floats.  Everything else is as in the
@@ -356,7 +357,8 @@ int cesm_wloss(const float* pred, const float* noise, const float* w, const int6
 int cesm_wloss_bwd(const float* pred, const float* noise, const float* w, const int64_t* row0, const float* a,
                    float lam, const float* gscale, float* dpred, int B, int V, int H, int W, int Hg,
                    hipStream_t stream);
-/* Ensemble verification statistics in one pass over the ensemble.  ens: [B][M][V][H][W] fp32, contiguous, member m of
+/* Ensemble verification statistics in one pass over the ensemble (csrc/ensemble.hip).
+ * ens: [B][M][V][H][W] fp32, contiguous, member m of
  * condition b = row b M + m of a sampler batch, 2 <= M <= 128; obs: [B][V][H][W] fp32 or NULL; w: [Hg] fp32 row weights,
  * Hg >= H; row0: [B] int64 grid row of each condition's row 0 (NULL: all 0).  Per pixel, evaluated in fp32 in this form
  * (the order of summation within a pixel is fixed but unspecified):
@@ -372,7 +374,7 @@ int cesm_wloss_bwd(const float* pred, const float* noise, const float* w, const 
  * Deterministic: no float atomics; per block fp32 partials in which a row's weight meets that row's sum once and rank
  * counts are integers until then; the blocks' partials are added in double in a fixed order by a second kernel (one
  * wave per accumulator entry).  ens is read once, 16 bytes per lane where W % 4 == 0 and ens is 16-byte aligned, else
- * 4; any W.  P is formed pairwise from LDS (csrc/ensemble.h has the layout); M is a run-time value and nothing is
+ * 4; any W.  P is formed pairwise from LDS (the source has the layout); M is a run-time value and nothing is
  * padded.  Non-finite inputs may give non-finite outputs; rank stays in [0, M].
  * CESM_EINVAL: ens or w null, M outside 2 .. 128, a size < 1, Hg < H, crps or rank without obs, acc without part, or
  * no output at all.  An added entry point (no existing argument list changed): the ABI version stays. */

@@ -241,7 +241,7 @@ SWEEP_FP32 = [(kind, F32, Nb, H, W, c1, c2, co, True)
 SWEEPS = {"3x3_full": SWEEP_3X3_FULL, "3x3_reduced": SWEEP_3X3_REDUCED, "s2": SWEEP_S2, "s2_generic": SWEEP_S2_GENERIC,
           "1x1": SWEEP_1X1, "fp32": SWEEP_FP32}
 
-# the complete name tables of cesm_conv_fwd_variant / cesm_conv_wgrad_variant (csrc/conv.hip kConvFwdVariantName,
+# the complete name tables of cesm_conv_fwd_variant / cesm_conv_wgrad_variant (csrc/conv_fwd.hip kConvFwdVariantName,
 # csrc/conv_wgrad.hip)
 FWD_NAMES = {
     "gemm1x1_kernel<128>", "gemm1x1_kernel<64>", "conv3x3p_kernel<32,7,true>", "conv3x3_bf16_kernel<36>",

@@ -1,4 +1,4 @@
-"""cesm_ens_stats on the GPU (csrc/ensemble.h, kernels.ens_stats) against the float64 reference of
+"""cesm_ens_stats on the GPU (csrc/ensemble.hip, kernels.ens_stats) against the float64 reference of
 tests/test_ensemble_host.py (ref64, written from the contract in include/cesm_hip.h).  Every tensor the wrapper
 allocates starts as NaN (the `poisoned` fixture; int32 maps as a negative pattern), so an element the kernel leaves out
 shows."""

@@ -77,7 +77,7 @@ L0_P, L0_WS = "conv3x3p_kernel<32,7,true>", "conv3x3ws_kernel<32>"
 
 
 def l0_var(H, W):
-    """the level-0 kernel the dispatch picks (mirror of conv.hip ws_tile: best pixel utilisation of the 256-pixel
+    """the level-0 kernel the dispatch picks (mirror of conv_fwd.hip ws_tile: best pixel utilisation of the 256-pixel
     tiles, TW in {32, 36}, TH <= 8, first maximum wins; >= 90 % -> warp-specialized)"""
     best, btw = -1.0, 32
     for tw in (32, 36):
