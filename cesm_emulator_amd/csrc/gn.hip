@@ -249,25 +249,40 @@ __device__ __forceinline__ void gn_coef8(const GnAffine& q, int b, int c0, int C
 
 // (Round 5: four rows per step with every load before the first store, GN_BATCH: whole step 61.58 / 61.83 ->
 // 61.75 / 61.89 samples/s, inside the spread; removed -- profiles/r5j_gn_batch_ab.txt.)
+// A row window of every sample: rows [lo, lo + n) of its rows_b (the centre frame, the only one the head reads).  The
+// WIN instantiations of the streaming kernels take the tensor that is zero / unused outside the window in compact
+// [B][n][C] form; the others ignore it.
+struct GnWin {
+  int64_t lo, n;
+};
+
+template <bool WIN>
+__device__ __forceinline__ bool gn_in_win(const GnWin& win, int64_t r) {
+  return !WIN || (r >= win.lo && r < win.lo + win.n);
+}
+
 // grid (nchunk, B): thread = (8-channel group c8, row lane rr), rows strided by 256/(C/8)
-template <typename T>
+// WIN: only the window rows of y are read (chunks over win.n rows); res and out are compact [B][win.n][C]
+template <typename T, bool WIN = false>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ y, const GnAffine coef,
                                                        const T* __restrict__ res, T* __restrict__ out, int64_t rows_b,
-                                                       int C, int nchunk) {
+                                                       int C, int nchunk, const GnWin win) {
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int cv = C / 8, rl = 256 / cv;
   const int c8 = threadIdx.x % cv, rr = threadIdx.x / cv;
   if (rr >= rl) return;
   float A1[8], A0[8];
   gn_coef8(coef, b, c8 * 8, C, A1, A0);
-  const int64_t rpc = (rows_b + nchunk - 1) / nchunk;
-  const int64_t r0 = chunk * rpc, r1 = min(rows_b, r0 + rpc);
-  const int64_t off = (int64_t)b * rows_b * C + c8 * 8;
+  const int64_t rows = WIN ? win.n : rows_b;  // rows of res / out per sample, and the rows the chunks cover
+  const int64_t rpc = (rows + nchunk - 1) / nchunk;
+  const int64_t r0 = chunk * rpc, r1 = min(rows, r0 + rpc);
+  const int64_t off = (int64_t)b * rows * C + c8 * 8;
+  const int64_t yoff = WIN ? ((int64_t)b * rows_b + win.lo) * C + c8 * 8 : off;
   int64_t r = r0 + rr;
 #pragma unroll 4
   for (; r < r1; r += rl) {
     float v[8], rv[8];
-    gl8(y + off + r * C, v);
+    gl8(y + yoff + r * C, v);
     if (res) gl8(res + off + r * C, rv);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -279,10 +294,16 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ y, 
 }
 
 // part[b][chunk][c] = (S1 = sum da, S3 = sum da*y, Sy = sum y)
-template <typename T, bool NT = true>
+// WIN: dout is compact [B][win.n][C] and zero outside the window: rows outside it do not read it and take d = 0.
+// They still run the row's arithmetic (da = 0 * silu' adds an exact zero to S1 and S3): the compiler contracts
+// S1 += d * silu' into an fma in the unrolled body and not in the remainder iterations, so a row's rounding depends
+// on its place in the thread's loop, and only the dense kernel's own loop over every row reproduces its sums bit
+// for bit.  Chunks and every thread's row order are the dense kernel's.
+template <typename T, bool NT = true, bool WIN = false>
 __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict__ dout, const T* __restrict__ y,
                                                             const GnAffine coef, float* __restrict__ part,
-                                                            int64_t rows_b, int C, int nchunk, int b0) {
+                                                            int64_t rows_b, int C, int nchunk, int b0,
+                                                            const GnWin win) {
   const int bl = blockIdx.y, b = bl + b0, chunk = blockIdx.x;
   const int cv = C / 8, rl = 256 / cv;
   const int tid = threadIdx.x;
@@ -293,16 +314,22 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
   const int64_t r0 = chunk * rpc, r1 = min(rows_b, r0 + rpc);
   const int64_t off = (int64_t)b * rows_b * C + c8 * 8;
   float s1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s3[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sy[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // WIN: window row r is row r - lo of the compact dout
+  const int64_t doff = WIN ? ((int64_t)b * win.n - win.lo) * C + c8 * 8 : off;
   if (rr < rl) {
 #pragma unroll 4
     for (int64_t r = r0 + rr; r < r1; r += rl) {
       float v[8], d[8];
       if (NT) {
         gl8(y + off + r * C, v);
-        gl8(dout + off + r * C, d);
+        gl8(dout + (gn_in_win<WIN>(win, r) ? doff + r * C : 0), d);
       } else {  // default policy: the lines stay in the Infinity Cache for gn_bwd_apply's re-read
         load8(y + off + r * C, v);
-        load8(dout + off + r * C, d);
+        load8(dout + (gn_in_win<WIN>(win, r) ? doff + r * C : 0), d);
+      }
+      if (!gn_in_win<WIN>(win, r)) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = 0.f;
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
@@ -463,11 +490,13 @@ __device__ __forceinline__ void gn_param_grad_block(const GnParamGrad& pg, int C
   }
 }
 
-template <typename T>
+// WIN: dout is compact [B][win.n][C]; rows outside the window take d = 0 without reading it and run the same
+// arithmetic (dy = 0*E1 + y*E2 + E3), for the reason given at the reduction
+template <typename T, bool WIN = false>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__ dout, const T* __restrict__ y,
                                                            const GnAffine coef, const float* __restrict__ E,
                                                            T* __restrict__ dy, int64_t rows_b, int C, int nchunk,
-                                                           int b0, const GnParamGrad pg) {
+                                                           int b0, const GnParamGrad pg, const GnWin win) {
   const int b = blockIdx.y + b0, chunk = blockIdx.x;
   if (blockIdx.x == 0 && blockIdx.y == 0) gn_param_grad_block(pg, C);
   const int cv = C / 8, rl = 256 / cv;
@@ -481,12 +510,17 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
   const int64_t rpc = (rows_b + nchunk - 1) / nchunk;
   const int64_t r0 = chunk * rpc, r1 = min(rows_b, r0 + rpc);
   const int64_t off = (int64_t)b * rows_b * C + c8 * 8;
+  const int64_t doff = WIN ? ((int64_t)b * win.n - win.lo) * C + c8 * 8 : off;
   int64_t r = r0 + rr;
 #pragma unroll 4
   for (; r < r1; r += rl) {
     float v[8], d[8];
     gl8(y + off + r * C, v);
-    gl8(dout + off + r * C, d);
+    gl8(dout + (gn_in_win<WIN>(win, r) ? doff + r * C : 0), d);
+    if (!gn_in_win<WIN>(win, r)) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) d[i] = 0.f;
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float da = d[i] * dsilu_t<T>(fmaf(v[i], A1[i], A0[i]));
@@ -551,27 +585,54 @@ int cesm_gn_stats_part(float* part, float* stats, int B, int64_t nslot, int C, i
   return cesm_launch_status();
 }
 
-int cesm_gn_apply(int dtype, const void* y, const float* stats, const float* gamma, const float* beta,
-                  const float* ss, const void* res, void* out, float* ws, int B, int64_t rows_b, int C, int G,
-                  hipStream_t stream) {
+static int gn_apply_launch(int dtype, const void* y, const float* stats, const float* gamma, const float* beta,
+                           const float* ss, const void* res, void* out, int B, int64_t rows_b, int C, int G,
+                           const GnWin* win, hipStream_t stream) {
   if (C % 8 || C / 8 > 256 || C % G) return CESM_EINVAL;
   const GnAffine aff{stats, gamma, beta, ss, G};
-  (void)ws;
-  const int nch = gn_apply_chunks(rows_b, C);
+  const int nch = gn_apply_chunks(win ? win->n : rows_b, C);
   int rc = dispatch_dt(dtype, [&](auto* tp) {
     using T = std::remove_pointer_t<decltype(tp)>;
-    gn_apply_kernel<T><<<dim3(nch, B), 256, 0, stream>>>((const T*)y, aff, (const T*)res, (T*)out, rows_b, C, nch);
+    if (win)
+      gn_apply_kernel<T, true><<<dim3(nch, B), 256, 0, stream>>>((const T*)y, aff, (const T*)res, (T*)out, rows_b, C,
+                                                                 nch, *win);
+    else
+      gn_apply_kernel<T><<<dim3(nch, B), 256, 0, stream>>>((const T*)y, aff, (const T*)res, (T*)out, rows_b, C, nch,
+                                                           GnWin{0, 0});
   });
   if (rc) return rc;
   return cesm_launch_status();
 }
 
+static bool gn_win_ok(int64_t rows_b, int64_t row_lo, int64_t row_n) {
+  return row_lo >= 0 && row_n > 0 && row_lo <= rows_b - row_n;
+}
+
+int cesm_gn_apply(int dtype, const void* y, const float* stats, const float* gamma, const float* beta,
+                  const float* ss, const void* res, void* out, float* ws, int B, int64_t rows_b, int C, int G,
+                  hipStream_t stream) {
+  (void)ws;
+  return gn_apply_launch(dtype, y, stats, gamma, beta, ss, res, out, B, rows_b, C, G, nullptr, stream);
+}
+
+// cesm_gn_apply on rows [row_lo, row_lo + row_n) of every sample: y full [B][rows_b][C] (only its window rows are
+// read), res_c (nullable) and out_c compact [B][row_n][C]
+int cesm_gn_apply_rows(int dtype, const void* y, const float* stats, const float* gamma, const float* beta,
+                       const float* ss, const void* res_c, void* out_c, float* ws, int B, int64_t rows_b, int C, int G,
+                       int64_t row_lo, int64_t row_n, hipStream_t stream) {
+  (void)ws;
+  if (!gn_win_ok(rows_b, row_lo, row_n)) return CESM_EINVAL;
+  const GnWin win{row_lo, row_n};
+  return gn_apply_launch(dtype, y, stats, gamma, beta, ss, res_c, out_c, B, rows_b, C, G, &win, stream);
+}
+
 // Backward of out = silu(GN(y)*(1+scale)+shift) (+res).  Writes dy, dss [B][2C] (if non-null),
 // dgamma/dbeta and the producing conv's bias gradient dbias = sum dy (each nullable; accumulate flag).
 // ws: float workspace >= B*1024*C*3 + B*C*3 + B*C*5 floats.
-int cesm_gn_bwd(int dtype, const void* dout, const void* y, const float* stats, const float* gamma,
-                const float* beta, const float* ss, void* dy, float* dss, float* dgamma, float* dbeta, float* dbias,
-                float* ws, int B, int64_t rows_b, int C, int G, int accumulate, hipStream_t stream) {
+static int gn_bwd_launch(int dtype, const void* dout, const void* y, const float* stats, const float* gamma,
+                         const float* beta, const float* ss, void* dy, float* dss, float* dgamma, float* dbeta,
+                         float* dbias, float* ws, int B, int64_t rows_b, int C, int G, int accumulate,
+                         const GnWin* win, hipStream_t stream) {
   if (C % 8 || C / 8 > 128 || C % G || C / G > 64 || 64 % (C / G) || G > 64) return CESM_EINVAL;
   const double count = (double)rows_b * (C / G);
   const GnAffine aff{stats, gamma, beta, ss, G};
@@ -582,17 +643,47 @@ int cesm_gn_bwd(int dtype, const void* dout, const void* y, const float* stats, 
   float* pb = part + (int64_t)B * nchunk * C * 3;
   float* coef = pb + (int64_t)B * C * 3;
   float* E = coef + (int64_t)B * C * 2;
+  const GnWin w = win ? *win : GnWin{0, 0};
+  const GnParamGrad pg{pb, dgamma, dbeta, dbias, B, accumulate};
   rc = dispatch_dt(dtype, [&](auto* tp) {
     using T = std::remove_pointer_t<decltype(tp)>;
-    gn_bwd_reduce_kernel<T><<<dim3(nchunk, B), 256, 0, stream>>>((const T*)dout, (const T*)y, aff, part, rows_b, C,
-                                                                 nchunk, 0);
+    if (win)
+      gn_bwd_reduce_kernel<T, true, true><<<dim3(nchunk, B), 256, 0, stream>>>((const T*)dout, (const T*)y, aff, part,
+                                                                               rows_b, C, nchunk, 0, w);
+    else
+      gn_bwd_reduce_kernel<T><<<dim3(nchunk, B), 256, 0, stream>>>((const T*)dout, (const T*)y, aff, part, rows_b, C,
+                                                                   nchunk, 0, w);
     gn_bwd_finalize_kernel<<<dim3(B, (unsigned)cdiv(C, 64)), 64 * GNF_KG, 0, stream>>>(part, stats, gamma, beta, ss, dss, pb,
                                                                                E, C, G, nchunk, count, (float)rows_b, 0);
-    gn_bwd_apply_kernel<T><<<dim3(nch, B), 256, 0, stream>>>((const T*)dout, (const T*)y, aff, E, (T*)dy, rows_b, C,
-                                                             nch, 0, GnParamGrad{pb, dgamma, dbeta, dbias, B, accumulate});
+    if (win)
+      gn_bwd_apply_kernel<T, true><<<dim3(nch, B), 256, 0, stream>>>((const T*)dout, (const T*)y, aff, E, (T*)dy,
+                                                                     rows_b, C, nch, 0, pg, w);
+    else
+      gn_bwd_apply_kernel<T><<<dim3(nch, B), 256, 0, stream>>>((const T*)dout, (const T*)y, aff, E, (T*)dy, rows_b, C,
+                                                               nch, 0, pg, w);
   });
   if (rc) return rc;
   return cesm_launch_status();
+}
+
+int cesm_gn_bwd(int dtype, const void* dout, const void* y, const float* stats, const float* gamma,
+                const float* beta, const float* ss, void* dy, float* dss, float* dgamma, float* dbeta, float* dbias,
+                float* ws, int B, int64_t rows_b, int C, int G, int accumulate, hipStream_t stream) {
+  return gn_bwd_launch(dtype, dout, y, stats, gamma, beta, ss, dy, dss, dgamma, dbeta, dbias, ws, B, rows_b, C, G,
+                       accumulate, nullptr, stream);
+}
+
+// cesm_gn_bwd for a dout that is zero outside rows [row_lo, row_lo + row_n) of every sample, given compact as dout_c
+// [B][row_n][C]; y and dy are full and dense, the workspace is cesm_gn_bwd's.  Results equal cesm_gn_bwd's on the
+// zero-padded dout (up to the sign of a zero).
+int cesm_gn_bwd_rows(int dtype, const void* dout_c, const void* y, const float* stats, const float* gamma,
+                     const float* beta, const float* ss, void* dy, float* dss, float* dgamma, float* dbeta,
+                     float* dbias, float* ws, int B, int64_t rows_b, int C, int G, int64_t row_lo, int64_t row_n,
+                     int accumulate, hipStream_t stream) {
+  if (!gn_win_ok(rows_b, row_lo, row_n)) return CESM_EINVAL;
+  const GnWin win{row_lo, row_n};
+  return gn_bwd_launch(dtype, dout_c, y, stats, gamma, beta, ss, dy, dss, dgamma, dbeta, dbias, ws, B, rows_b, C, G,
+                       accumulate, &win, stream);
 }
 
 }  // extern "C"

@@ -530,6 +530,15 @@ __global__ void add_kernel(const T* __restrict__ a, const T* __restrict__ b, T* 
   }
 }
 
+// grid (blocks, B): sample b's n16 16-byte units from src + b * sstride to dst + b * dstride (strides in units)
+__global__ __launch_bounds__(256) void rows_copy_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst,
+                                                        int64_t n16, int64_t sstride, int64_t dstride) {
+  const uint4* s = src + blockIdx.y * sstride;
+  uint4* d = dst + blockIdx.y * dstride;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n16; e += (int64_t)gridDim.x * blockDim.x)
+    d[e] = s[e];
+}
+
 template <typename TI, typename TO>
 __global__ void cast_kernel(const TI* __restrict__ x, TO* __restrict__ y, int64_t n) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
@@ -746,6 +755,33 @@ int cesm_add(int dtype, const void* a, const void* b, void* out, int64_t n, hipS
   else
     return CESM_EINVAL;
   return cesm_launch_status();
+}
+
+// rows [row_lo, row_lo + row_n) of every sample of a [B][rows_b][C] tensor <-> compact [B][row_n][C]: per sample one
+// contiguous run of row_n * C elements, copied 16 bytes per lane
+static int rows_copy(int dtype, const void* src, void* dst, int B, int64_t rows_b, int64_t row_lo, int64_t row_n, int C,
+                     bool gather, hipStream_t stream) {
+  const int64_t es = dtype == CESM_DT_BF16 ? 2 : dtype == CESM_DT_F32 ? 4 : 0;
+  if (!es || B <= 0 || B > 65535 || C <= 0 || (C * es) % 16 || row_lo < 0 || row_n <= 0 || row_lo > rows_b - row_n ||
+      (((uintptr_t)src | (uintptr_t)dst) & 15))
+    return CESM_EINVAL;
+  const int64_t u = C * es / 16;  // 16-byte units per row
+  const int64_t n16 = row_n * u, full = rows_b * u, lo = row_lo * u;
+  const unsigned grid = (unsigned)std::min<int64_t>(cdiv(n16, 256), 4096);
+  const uint4* s = (const uint4*)src + (gather ? lo : 0);
+  uint4* d = (uint4*)dst + (gather ? 0 : lo);
+  rows_copy_kernel<<<dim3(grid, B), 256, 0, stream>>>(s, d, n16, gather ? full : n16, gather ? n16 : full);
+  return cesm_launch_status();
+}
+
+int cesm_rows_gather(int dtype, const void* src, void* dst, int B, int64_t rows_b, int64_t row_lo, int64_t row_n, int C,
+                     hipStream_t stream) {
+  return rows_copy(dtype, src, dst, B, rows_b, row_lo, row_n, C, true, stream);
+}
+
+int cesm_rows_scatter(int dtype, const void* src, void* dst, int B, int64_t rows_b, int64_t row_lo, int64_t row_n, int C,
+                      hipStream_t stream) {
+  return rows_copy(dtype, src, dst, B, rows_b, row_lo, row_n, C, false, stream);
 }
 
 int cesm_cast(int dtype_in, int dtype_out, const void* x, void* y, int64_t n, hipStream_t stream) {

@@ -393,6 +393,67 @@ def gn_bwd(dout, y, stats, gamma, beta, ss, dgamma, dbeta, B, G, want_dss, dbias
     return dy, dss
 
 
+def _row_window(t, B, row_lo, row_n):
+    """(C, rows_b) of the full tensor t [B * frames, H, W, C] after checking the window [row_lo, row_lo + row_n)"""
+    _chk(t)
+    C = t.shape[-1]
+    rows_b = t.numel() // (C * B)
+    if t.numel() != B * rows_b * C or row_lo < 0 or row_n <= 0 or row_lo + row_n > rows_b:
+        raise RuntimeError(f"row window [{row_lo}, {row_lo + row_n}) outside the {rows_b} rows of a sample")
+    return C, rows_b
+
+
+def gn_apply_rows(y, stats, gamma, beta, ss, res_c, B, G, row_lo, row_n):
+    """gn_apply on rows [row_lo, row_lo + row_n) of every sample: y full, res_c (or None) and the result compact
+    [B, row_n, C]"""
+    C, rows_b = _row_window(y, B, row_lo, row_n)
+    out = empty((B, row_n, C), y.dtype, y.device)
+    if res_c is not None:
+        _chk(res_c, dtype=y.dtype)
+        if res_c.numel() != out.numel():
+            raise RuntimeError(f"gn_apply_rows: res_c has {res_c.numel()} elements, expected {out.numel()}")
+    ws = empty((2 * B * C,), torch.float32, y.device)
+    call("cesm_gn_apply_rows", dtcode(y), P(y), P(stats), P(gamma), P(beta), P(ss), P(res_c), P(out), P(ws), B, rows_b,
+         C, G, row_lo, row_n, S())
+    return out
+
+
+def gn_bwd_rows(dout_c, y, stats, gamma, beta, ss, dgamma, dbeta, B, G, want_dss, row_lo, row_n, dbias=None):
+    """gn_bwd for a dout that is zero outside rows [row_lo, row_lo + row_n) of every sample, given compact as dout_c
+    [B, row_n, C]; returns the dense dy (y's shape) and dss"""
+    C, rows_b = _row_window(y, B, row_lo, row_n)
+    _chk(dout_c, dtype=y.dtype)
+    if dout_c.numel() != B * row_n * C:
+        raise RuntimeError(f"gn_bwd_rows: dout_c has {dout_c.numel()} elements, expected {B * row_n * C}")
+    dy = empty(y.shape, y.dtype, y.device)
+    dss = empty((B, 2 * C), torch.float32, y.device) if want_dss else None
+    ws = empty((max(B * 1024, 1024) * C * 3 + B * C * 3 + B * C * 5,), torch.float32, y.device)
+    call("cesm_gn_bwd_rows", dtcode(y), P(dout_c), P(y), P(stats), P(gamma), P(beta), P(ss), P(dy), P(dss), P(dgamma),
+         P(dbeta), P(dbias), P(ws), B, rows_b, C, G, row_lo, row_n, 1, S())
+    return dy, dss
+
+
+def rows_gather(x, B, row_lo, row_n, out_shape=None):
+    """rows [row_lo, row_lo + row_n) of every sample of x [B * frames, H, W, C] as a compact tensor [B, row_n, C]
+    (or out_shape with as many elements)"""
+    C, rows_b = _row_window(x, B, row_lo, row_n)
+    out = empty((B, row_n, C) if out_shape is None else out_shape, x.dtype, x.device)
+    if out.numel() != B * row_n * C:
+        raise RuntimeError(f"rows_gather: out_shape {tuple(out.shape)} does not hold {B} x {row_n} x {C} elements")
+    call("cesm_rows_gather", dtcode(x), P(x), P(out), B, rows_b, row_lo, row_n, C, S())
+    return out
+
+
+def rows_scatter(src_c, dst, B, row_lo, row_n):
+    """overwrite rows [row_lo, row_lo + row_n) of every sample of dst with the compact src_c; other rows untouched"""
+    C, rows_b = _row_window(dst, B, row_lo, row_n)
+    _chk(src_c, dtype=dst.dtype)
+    if src_c.numel() != B * row_n * C:
+        raise RuntimeError(f"rows_scatter: src_c has {src_c.numel()} elements, expected {B * row_n * C}")
+    call("cesm_rows_scatter", dtcode(dst), P(src_c), P(dst), B, rows_b, row_lo, row_n, C, S())
+    return dst
+
+
 def ln_fwd(x, gamma, save=True, eps=1e-5, perm=None):
     """perm = (F, HW): write the output rows of voxel (b, f, p) at (b, p, f) -- pixel-major, a pixel's frames
     adjacent (mr stays in x's order)"""

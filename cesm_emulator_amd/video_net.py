@@ -241,6 +241,13 @@ def conv_backward(rc, spec, st, dy, need_dx=True, dres1=None, dres2=None, bias_d
         conv_param_grads(spec, st, dy, dw, None if bias_done else db)
     if not need_dx:
         return None
+    return conv_dgrad(rc, spec, st, dy, dres1, dres2)
+
+
+def conv_dgrad(rc, spec, st, dy, dres1=None, dres2=None):
+    """dX of the conv recorded in st (split for concat inputs) + fused residual grads.  The image count is dy's, so a
+    dy of fewer images than the forward's (the centre frames) gives the dX of those images."""
+    w = spec.mod.weight
     k = spec.k
     Nb, H, W, C1 = st.x1.shape
     cin = spec.cin
@@ -382,8 +389,31 @@ def _flat(p):
 GN_EPI_STATS = True
 
 
-def block_fwd(rc, blk, x1, x2, ss, res):
-    """Block (video_net.py:212-227): conv3x3 -> GroupNorm -> scale/shift -> SiLU (+res)."""
+# The model returns frame F // 2 only (the head reads no other), so the tail of out_conv[0] -- the residual 1x1 conv,
+# the last GroupNorm's apply and everything the backward derives from the head's gradient alone -- runs on the centre
+# frames' B images instead of all B * F.  Module switch: False takes the all-frames path everywhere.
+CENTER_TAIL = True
+
+
+def center_window(rc, rb, x1, x2):
+    """(row_lo, row_n) of the centre frame within a sample's rows if out_conv[0] = rb can take the centre-frame
+    tail on inputs x1, x2, else None (the all-frames path)"""
+    if not CENTER_TAIL or rc.F <= 1 or rb.mlp is not None or isinstance(rb.res_conv, nn.Identity):
+        return None
+    if x1.dtype not in (torch.bfloat16, torch.float32):
+        return None
+    per16 = 16 // x1.element_size()  # the frame copies move 16 bytes per lane
+    chans = [x1.shape[3], rb.block1.proj.out_channels] + ([] if x2 is None else [x2.shape[3]])
+    if any(c % per16 for c in chans):
+        return None
+    HW = x1.shape[1] * x1.shape[2]
+    return (rc.F // 2) * HW, HW
+
+
+def block_fwd(rc, blk, x1, x2, ss, res, win=None):
+    """Block (video_net.py:212-227): conv3x3 -> GroupNorm -> scale/shift -> SiLU (+res).
+    win = (row_lo, row_n): the conv and the statistics on all frames, the rest on that row window of every sample only:
+    res is compact [B, H, W, C] and so is the result."""
     spec = ConvSpec(blk.proj)
     G = blk.norm.num_groups
     Nb, H, W, _ = x1.shape
@@ -401,21 +431,43 @@ def block_fwd(rc, blk, x1, x2, ss, res):
     else:
         y, cst = conv_forward(rc, spec, x1, x2)
         stats = K.gn_stats(y, rc.B, G, blk.norm.eps)
-    out = K.gn_apply(y, stats, blk.norm.weight, blk.norm.bias, ss, res, rc.B, G)
+    if win is None:
+        out = K.gn_apply(y, stats, blk.norm.weight, blk.norm.bias, ss, res, rc.B, G)
+    else:
+        out = K.gn_apply_rows(y, stats, blk.norm.weight, blk.norm.bias, ss, res, rc.B, G, *win)
+        out = out.view(rc.B, geom_hw[0], geom_hw[1], spec.cout)
     st = SimpleNamespace(spec=spec, cst=cst, y=y, stats=stats, ss=ss) if rc.save else None
     return out, st
 
 
-def block_bwd(rc, blk, st, dout, want_dss, dres1=None, dres2=None):
+def block_bwd(rc, blk, st, dout, want_dss, dres1=None, dres2=None, win=None, dres_win=None):
+    """win: dout is the compact gradient of block_fwd(win=...)'s result.  dres_win: dres1 / dres2 are compact residual
+    gradients that are zero outside that row window of every sample."""
     G = blk.norm.num_groups
-    dy, dss = K.gn_bwd(dout, st.y, st.stats, blk.norm.weight, blk.norm.bias, st.ss, gbuf(blk.norm.weight),
-                       gbuf(blk.norm.bias), rc.B, G, want_dss, dbias=gbuf(blk.proj.bias))
-    dx = conv_backward(rc, st.spec, st.cst, dy, True, dres1, dres2, bias_done=True)
+    if win is None:
+        dy, dss = K.gn_bwd(dout, st.y, st.stats, blk.norm.weight, blk.norm.bias, st.ss, gbuf(blk.norm.weight),
+                           gbuf(blk.norm.bias), rc.B, G, want_dss, dbias=gbuf(blk.proj.bias))
+    else:
+        dy, dss = K.gn_bwd_rows(dout, st.y, st.stats, blk.norm.weight, blk.norm.bias, st.ss, gbuf(blk.norm.weight),
+                                gbuf(blk.norm.bias), rc.B, G, want_dss, *win, dbias=gbuf(blk.proj.bias))
+    if dres_win is None:
+        dx = conv_backward(rc, st.spec, st.cst, dy, True, dres1, dres2, bias_done=True)
+        return dx, dss
+    # the dgrad over all frames without residuals, then the window's images again with them: the epilogue adds the
+    # residual to the fp32 accumulator before rounding, as the all-frames call with the zero-padded residual would,
+    # and the rows outside the window had a residual of exactly zero
+    dx = conv_backward(rc, st.spec, st.cst, dy, True, bias_done=True)
+    Nb, H, W, C = dy.shape
+    dy_c = K.rows_gather(dy, rc.B, *dres_win, out_shape=(rc.B, H, W, C))
+    dx_c = conv_dgrad(rc, st.spec, st.cst, dy_c, dres1, dres2)
+    for full, part in zip(dx, dx_c) if isinstance(dx, tuple) else ((dx, dx_c),):
+        K.rows_scatter(part, full, rc.B, *dres_win)
     return dx, dss
 
 
-def resnet_fwd(rc, rb, x1, x2=None, temb=None):
-    """ResnetBlock (video_net.py:230-265)."""
+def resnet_fwd(rc, rb, x1, x2=None, temb=None, win=None):
+    """ResnetBlock (video_net.py:230-265).  win (center_window): only that row window of the result is needed; the
+    result is then compact [B, H, W, C]."""
     ss = None
     if rb.mlp is not None:
         lin = rb.mlp[1]
@@ -426,20 +478,25 @@ def resnet_fwd(rc, rb, x1, x2=None, temb=None):
         r = x1
     else:
         rspec = ConvSpec(rb.res_conv)
+        if win is not None:  # the residual is added after the GroupNorm: the window's images only (kept for the wgrad)
+            Nb, H, W, _ = x1.shape
+            x1 = K.rows_gather(x1, rc.B, *win, out_shape=(rc.B, H, W, x1.shape[3]))
+            x2 = None if x2 is None else K.rows_gather(x2, rc.B, *win, out_shape=(rc.B, H, W, x2.shape[3]))
         r, rst = conv_forward(rc, rspec, x1, x2)
-    out, st2 = block_fwd(rc, rb.block2, h, None, None, r)
-    st = SimpleNamespace(st1=st1, st2=st2, rst=rst, temb=temb) if rc.save else None
+    out, st2 = block_fwd(rc, rb.block2, h, None, None, r, win)
+    st = SimpleNamespace(st1=st1, st2=st2, rst=rst, temb=temb, win=win) if rc.save else None
     return out, st
 
 
 def resnet_bwd(rc, rb, st, dout):
-    dh, _ = block_bwd(rc, rb.block2, st.st2, dout, False)
+    """dout: gradient of resnet_fwd's result (compact when the forward ran with a window)"""
+    dh, _ = block_bwd(rc, rb.block2, st.st2, dout, False, win=st.win)
     if isinstance(rb.res_conv, nn.Identity):
         dr = (dout, None)
     else:
-        r = conv_backward(rc, ConvSpec(rb.res_conv), st.rst, dout, True)
+        r = conv_backward(rc, ConvSpec(rb.res_conv), st.rst, dout, True)  # compact operands under a window
         dr = r if isinstance(r, tuple) else (r, None)
-    dx, dss = block_bwd(rc, rb.block1, st.st1, dh, rb.mlp is not None, dr[0], dr[1])
+    dx, dss = block_bwd(rc, rb.block1, st.st1, dh, rb.mlp is not None, dr[0], dr[1], dres_win=st.win)
     if rb.mlp is not None:
         lin = rb.mlp[1]
         K.linear_small_bwd(st.temb, lin.weight, dss, rc.dt, gbuf(lin.weight), gbuf(lin.bias), True, True)
@@ -812,11 +869,25 @@ class UNetModel3D(nn.Module):
             if not isinstance(up, nn.Identity):
                 x, s.up = conv_forward(rc, ConvSpec(up), x)
             tape.ups.append(s)
-        x, tape.out_rb = resnet_fwd(rc, self.out_conv[0], x, r, None)
-        head = self.out_conv[1]
-        out = K.head_fwd(x, head.weight, head.bias, B, F)
-        tape.head_in = x
+        out = self.out_forward(rc, x, r, tape)
         return (out, tape) if save else out
+
+    def out_forward(self, rc, x, r, tape):
+        """out_conv on cat(x, r): the ResnetBlock and the head on frame F // 2 -> [B, V, H, W] fp32"""
+        win = center_window(rc, self.out_conv[0], x, r)
+        x, tape.out_rb = resnet_fwd(rc, self.out_conv[0], x, r, None, win)
+        head = self.out_conv[1]
+        tape.head_F = rc.F if win is None else 1  # with a window x is [B, H, W, C], the centre frames: frame 0 of 1
+        out = K.head_fwd(x, head.weight, head.bias, rc.B, tape.head_F)
+        tape.head_in = x
+        return out
+
+    def out_backward(self, rc, dout, tape):
+        """backward of out_forward: the gradients of x and r (dense, all frames)"""
+        head = self.out_conv[1]
+        hw, hb = gbuf(head.weight), gbuf(head.bias)
+        dx = K.head_bwd(dout.contiguous(), tape.head_in, head.weight, hw, hb, rc.B, tape.head_F)
+        return resnet_bwd(rc, self.out_conv[0], tape.out_rb, dx)
 
     def backward_from(self, dout, tape, want_xt=False, want_cond=False, param_grads=True):
         """backward of the forward that recorded `tape` (held by that forward's autograd node, so several
@@ -844,10 +915,7 @@ class UNetModel3D(nn.Module):
             rc.wstream = _wgrad_stream(dev)
         rc.dt = torch.zeros((rc.B, self.time_mlp[1].out_features), dtype=torch.float32, device=dev)
         rc.dtable = gbuf(self.time_rel_pos_bias.relative_attention_bias.weight)
-        head = self.out_conv[1]
-        hw, hb = gbuf(head.weight), gbuf(head.bias)
-        dx = K.head_bwd(dout.contiguous(), tape.head_in, head.weight, hw, hb, rc.B, rc.F)
-        dx, dr = resnet_bwd(rc, self.out_conv[0], tape.out_rb, dx)
+        dx, dr = self.out_backward(rc, dout, tape)
         done(self.out_conv)
         nres = len(self.downs)
         dskips = [None] * nres

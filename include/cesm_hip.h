@@ -171,6 +171,21 @@ int cesm_gn_apply(int dtype, const void* y, const float* stats, const float* gam
 int cesm_gn_bwd(int dtype, const void* dout, const void* y, const float* stats, const float* gamma,
                 const float* beta, const float* ss, void* dy, float* dss, float* dgamma, float* dbeta, float* dbias,
                 float* ws, int B, int64_t rows_b, int C, int G, int accumulate, hipStream_t stream);
+/* Row-window forms for the tail of the network, where only the centre frame reaches the head: the window is rows
+ * [row_lo, row_lo + row_n) of every sample's rows_b (frame f: row_lo = f*H*W, row_n = H*W).  y (and dy) are the full
+ * [B][rows_b][C] tensors with the statistics of all rows; the tensors that matter only inside the window are compact
+ * [B][row_n][C].  cesm_gn_apply_rows reads only the window rows of y and writes only out_c (res_c nullable), with
+ * cesm_gn_apply's arithmetic.  cesm_gn_bwd_rows takes the compact dout_c of a dout that is zero outside the window
+ * and writes the dense dy and the same dss / dgamma / dbeta / dbias (each nullable) as cesm_gn_bwd would on the
+ * zero-padded dout, bit for bit up to the sign of a zero: rows outside the window read y, never dout_c.  ws as for the dense
+ * calls.  (Added without a CESM_ABI_VERSION bump: no existing argument list changed.) */
+int cesm_gn_apply_rows(int dtype, const void* y, const float* stats, const float* gamma, const float* beta,
+                       const float* ss, const void* res_c, void* out_c, float* ws, int B, int64_t rows_b, int C, int G,
+                       int64_t row_lo, int64_t row_n, hipStream_t stream);
+int cesm_gn_bwd_rows(int dtype, const void* dout_c, const void* y, const float* stats, const float* gamma,
+                     const float* beta, const float* ss, void* dy, float* dss, float* dgamma, float* dbeta,
+                     float* dbias, float* ws, int B, int64_t rows_b, int C, int G, int64_t row_lo, int64_t row_n,
+                     int accumulate, hipStream_t stream);
 /* channel LayerNorm (biased var, gamma only): video_net.py:78-87.  perm_f > 0: x is [B][perm_f][perm_hw] voxels and
  * out is written pixel-major ([B][perm_hw][perm_f], the long-window qkv order); 0: same order as x */
 int cesm_ln_fwd(int dtype, const void* x, const float* gamma, void* out, float* mr, int64_t V, int C, float eps,
@@ -405,6 +420,14 @@ int cesm_adamw_ema(float* p, float* g, float* m, float* v, float* info, int* ste
                    int warmup, hipStream_t stream);
 /* out = a + b (gradient sums at residual / skip fan-outs) */
 int cesm_add(int dtype, const void* a, const void* b, void* out, int64_t n, hipStream_t stream);
+/* Strided frame copy (csrc/misc.hip): gather copies rows [row_lo, row_lo + row_n) of every sample of src
+ * [B][rows_b][C] into the compact dst [B][row_n][C]; scatter copies the compact src over those rows of the full dst
+ * and touches no other row.  No host synchronisation (capture-safe).  C * element size must be a multiple of 16
+ * bytes and both pointers 16-byte aligned, else CESM_EINVAL.  (Added without a CESM_ABI_VERSION bump.) */
+int cesm_rows_gather(int dtype, const void* src, void* dst, int B, int64_t rows_b, int64_t row_lo, int64_t row_n, int C,
+                     hipStream_t stream);
+int cesm_rows_scatter(int dtype, const void* src, void* dst, int B, int64_t rows_b, int64_t row_lo, int64_t row_n, int C,
+                      hipStream_t stream);
 int cesm_cast(int dtype_in, int dtype_out, const void* x, void* y, int64_t n, hipStream_t stream);
 /* WindowedAllMembersDataset_random.__getitem__ gather (dataset_single_member.py:168-196);
  * items: nitems x {t0, m, anchor, reverse, crop_i, crop_j} int64 */
