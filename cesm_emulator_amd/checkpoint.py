@@ -15,9 +15,20 @@ import torch
 from .model import UNet, Diffusion
 
 
-def save_checkpoint(path, diffusion, optimizer, epoch, config, ema=None):
+def _plain_norm(norm):
+    """norm (data.load_fields) as plain lists of floats / strings: what torch.load(weights_only=True) reads back"""
+    out = {}
+    for k in ("cond_vars", "target_vars"):
+        out[k] = [str(v) for v in norm.get(k, [])]
+    for k in ("cond_mean", "cond_std", "target_mean", "target_std"):
+        out[k] = [float(v) for v in norm[k]]
+    return out
+
+
+def save_checkpoint(path, diffusion, optimizer, epoch, config, ema=None, norm=None):
     """train.py:1154-1165.  ema (an ema.EMA): its state_dict() goes under a further top-level key "ema"; the
-    reference's readers index ckpt["model"] / use .get(...) and ignore it."""
+    reference's readers index ckpt["model"] / use .get(...) and ignore it.  norm (data.load_fields' statistics): stored
+    under a further top-level key "norm", ignored by the reference's readers in the same way."""
     full = diffusion.state_dict()
     model_sd = {k[len("model."):]: v for k, v in full.items() if k.startswith("model.")}
     diff_buf = {k: v for k, v in full.items() if not k.startswith("model.")}
@@ -25,6 +36,8 @@ def save_checkpoint(path, diffusion, optimizer, epoch, config, ema=None):
             "optimizer": optimizer.state_dict() if optimizer is not None else {}, "config": config}
     if ema is not None:
         ckpt["ema"] = ema.state_dict()
+    if norm is not None:
+        ckpt["norm"] = _plain_norm(norm)
     torch.save(ckpt, path)
 
 
@@ -67,10 +80,14 @@ def build_from_config(cfg, device):
 
 def load_diffusion_from_checkpoint(ckpt_path, device="cuda", use_ema=False):
     """inference.py:47-73: returns (diffusion in eval mode with frozen parameters, config).  use_ema=True loads the
-    EMA of the weights (ckpt["ema"]["model"]) instead of the raw ones; KeyError if the checkpoint has none."""
+    EMA of the weights (ckpt["ema"]["model"]) instead of the raw ones; KeyError if the checkpoint has none.  A
+    checkpoint saved with norm= hands the statistics back as config["norm"] (for data.denormalize, summarize(scale=))."""
     dev = torch.device(device)
     ckpt = torch.load(ckpt_path, map_location=dev, weights_only=True)
     cfg = ckpt.get("config", {})
+    if ckpt.get("norm") is not None:
+        cfg = dict(cfg)
+        cfg["norm"] = ckpt["norm"]
     if use_ema:
         if not ckpt.get("ema") or "model" not in ckpt["ema"]:
             raise KeyError(f"{ckpt_path} holds no EMA of the weights (saved without ema=)")

@@ -22,11 +22,17 @@ from .model import check_row0, latitude_weights
 SCALARS = ("mse", "rmse", "var", "spread", "ssr", "crps", "rank_hist")
 
 
-def summarize(acc, members, has_obs=True):
+def norm_scale(norm):
+    """summarize()'s scale from normalisation statistics (data.load_fields' norm; None passes through)"""
+    return None if norm is None else norm["target_std"]
+
+
+def summarize(acc, members, has_obs=True, scale=None):
     """The per-variable scalars of an accumulator acc [V, 4 + M + 1] (float64; columns: sum w, sum w (mean - obs)^2,
     sum w var, sum w crps, sum w [rank = r] for r = 0 .. M), as float64 tensors on acc's device: mse, rmse, var, spread,
     ssr, crps are [V]; rank_hist [V, M + 1] holds weighted fractions that sum to 1.  has_obs=False: only var and spread
-    are formed, the others are None."""
+    are formed, the others are None.  scale [V] (the variables' target_std): results in physical units -- rmse, spread
+    and crps times scale[v], mse and var times scale[v]^2; ssr and rank_hist have no unit and stay."""
     M = int(members)
     if acc.ndim != 2 or acc.shape[1] != 4 + M + 1:
         raise ValueError(f"acc must be [V, {4 + M + 1}] for {M} members, got {tuple(acc.shape)}")
@@ -40,6 +46,13 @@ def summarize(acc, members, has_obs=True):
         hist = acc[:, 4:]
         out.update(mse=mse, rmse=mse.sqrt(), crps=acc[:, 3] / sw, ssr=((M + 1) / M * var / mse).sqrt(),
                    rank_hist=hist / hist.sum(dim=1, keepdim=True))
+    if scale is not None:
+        sc = torch.as_tensor(scale, dtype=torch.float64, device=acc.device).reshape(-1)
+        if sc.numel() != acc.shape[0]:
+            raise ValueError(f"scale must have one entry per variable ({acc.shape[0]}), got {sc.numel()}")
+        for k, f in (("rmse", sc), ("spread", sc), ("crps", sc), ("mse", sc * sc), ("var", sc * sc)):
+            if out[k] is not None:
+                out[k] = out[k] * f
     return out
 
 
@@ -109,8 +122,9 @@ class EnsembleVerifier:
         row0 = check_row0(row0, B, H, w.numel(), ens.device, has_lat=self.lat is not None)
         K.ens_stats(ens, obs, w, row0, mean=False, var=False, crps=False, rank=False, acc=self.acc, accumulate=True)
 
-    def result(self):
-        return summarize(self.acc, self.members)
+    def result(self, norm=None):
+        """summarize() over everything seen; norm (data.load_fields' statistics): in physical units"""
+        return summarize(self.acc, self.members, scale=norm_scale(norm))
 
     def reset(self):
         self.acc.zero_()

@@ -1044,6 +1044,87 @@ def window_gather(cond, tgt, items, K, h, w, center):
     return cwin, x0
 
 
+GATHER_MAX_V = 4  # cesm_window_gather_mv takes csel by value
+
+
+def _gather_range(name, a, lo, hi):
+    """ValueError naming the field and the first value of the CPU int64 tensor a outside [lo, hi]"""
+    bad = (a < lo) | (a > hi)
+    if bool(bad.any()):
+        raise ValueError(f"window_gather_mv: {name} = {int(a[bad][0])} outside [{lo}, {hi}]")
+
+
+def window_gather_mv(cond, tgt, times, meta, csel, h, w, out=None):
+    """V-variable window gather (cesm_window_gather_mv; the contract is in include/cesm_hip.h): cond [T, M, Vc, H, W]
+    and tgt [T, M, V, H, W] fp32 on the GPU, times [n, K] and meta [n, 4] = (member, anchor, i, j) int64, csel: V
+    indices into the Vc forcing planes.  Returns cwin [n, V, K, h, w], x0 [n, V, h, w] (out: that pair, to write into
+    instead of allocating).
+
+    CPU times / meta (what the loaders draw) are range-checked here, before anything is launched, and reach the device
+    through one pinned staging buffer with a non-blocking copy; device times / meta are passed as they are and not read
+    back (the kernel clamps every index)."""
+    for name, t, nd in (("cond", cond, 5), ("tgt", tgt, 5), ("times", times, 2), ("meta", meta, 2)):
+        if not torch.is_tensor(t) or t.ndim != nd:
+            raise RuntimeError(f"shape mismatch: {name} must be {nd}-D, got "
+                               f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    T, M, Vc, H, W = cond.shape
+    V = tgt.shape[2]
+    if tuple(tgt.shape) != (T, M, V, H, W):
+        raise RuntimeError(f"shape mismatch: tgt {tuple(tgt.shape)} against cond {tuple(cond.shape)}")
+    n, K = times.shape
+    if tuple(meta.shape) != (n, 4):
+        raise RuntimeError(f"shape mismatch: meta must be {(n, 4)}, got {tuple(meta.shape)}")
+    for name, t, dt in (("cond", cond, torch.float32), ("tgt", tgt, torch.float32), ("times", times, torch.int64),
+                        ("meta", meta, torch.int64)):
+        if t.dtype != dt:
+            raise RuntimeError(f"dtype mismatch: {name} is {t.dtype}, expected {dt}")
+    h, w = int(h), int(w)
+    csel = [int(c) for c in csel]
+    if not 1 <= V <= GATHER_MAX_V or len(csel) != V or K < 1 or n < 1 or min(T, M, Vc, h, w) < 1 or h > H or w > W:
+        raise ValueError(f"window_gather_mv: unsupported shape V={V} (1 .. {GATHER_MAX_V}) csel={csel} K={K} n={n} "
+                         f"crop {h} x {w} of {H} x {W}")
+    for c in csel:
+        if not 0 <= c < Vc:
+            raise ValueError(f"window_gather_mv: csel = {c} outside [0, {Vc - 1}]")
+    if times.device != meta.device:
+        raise RuntimeError(f"tensors on different devices: {times.device} and {meta.device}")
+    if not times.is_cuda:
+        _gather_range("times", times, 0, T - 1)
+        _gather_range("member (meta[:, 0])", meta[:, 0], 0, M - 1)
+        _gather_range("anchor (meta[:, 1])", meta[:, 1], 0, T - 1)
+        _gather_range("i (meta[:, 2])", meta[:, 2], 0, H - h)
+        _gather_range("j (meta[:, 3])", meta[:, 3], 0, W - w)
+    _chk(cond)
+    _chk(tgt)
+    if tgt.device != cond.device:
+        raise RuntimeError(f"tensors on different devices: {tgt.device} and {cond.device}")
+    if times.is_cuda:
+        _chk(times)
+        _chk(meta)
+        if times.device != cond.device:
+            raise RuntimeError(f"tensors on different devices: {times.device} and {cond.device}")
+    else:
+        # one pinned block (the caching host allocator keeps it until the copy below has run), one copy, no synchronise
+        stage = torch.empty(n * (K + 4), dtype=torch.int64, pin_memory=True)
+        stage[:n * K].view(n, K).copy_(times)
+        stage[n * K:].view(n, 4).copy_(meta)
+        both = stage.to(cond.device, non_blocking=True)
+        times, meta = both[:n * K].view(n, K), both[n * K:].view(n, 4)
+    if out is None:
+        cwin = empty((n, V, K, h, w), torch.float32, cond.device)
+        x0 = empty((n, V, h, w), torch.float32, cond.device)
+    else:
+        cwin, x0 = out
+        _chk(cwin, (n, V, K, h, w), torch.float32)
+        _chk(x0, (n, V, h, w), torch.float32)
+        if cwin.device != cond.device or x0.device != cond.device:
+            raise RuntimeError(f"tensors on different devices: {cwin.device}, {x0.device} and {cond.device}")
+    cs = csel + [0] * (GATHER_MAX_V - V)
+    _mv_call("cesm_window_gather_mv", f"V={V} Vc={Vc} csel={csel} K={K} crop {h} x {w} of {H} x {W}", P(cond), P(tgt),
+             P(times), P(meta), P(cwin), P(x0), n, K, V, Vc, *cs, T, M, H, W, h, w, S())
+    return cwin, x0
+
+
 def conv_fwd_variant(dtype, Nb, Hi, Wi, C1, C2, Ho, Wo, Cout, Co1, KH, KW, S, P, U):
     """name of the kernel cesm_conv_fwd selects for these arguments (host-only query)"""
     return lib().cesm_conv_fwd_variant(_DT[dtype], Nb, Hi, Wi, C1, C2, Ho, Wo, Cout, Co1, KH, KW, S, P, U).decode()

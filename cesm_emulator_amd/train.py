@@ -169,14 +169,15 @@ def train_one_epoch(diffusion, dl, optimizer, device, max_grad_norm=1.0, use_amp
 
 
 def validate_ensemble(diffusion, loader, members, steps=None, ddim_eta=0.0, member_batch=None, max_batches=None,
-                      ema=None):
+                      ema=None, norm=None):
     """Ensemble verification over a loader of (cond, target) batches: per batch, `members` samples per condition
     (Diffusion.sample_ensemble with steps / ddim_eta / member_batch) are judged against the loader's target with the
     batch's crop row offsets (`loader.last_row0`; a loader without it: no crop), all batches accumulated on the device
     (ensemble.EnsembleVerifier, one kernel call per batch, no host synchronisation).  Returns the verifier's result():
     per-variable mse, rmse, var, spread, ssr, crps and rank_hist, area-weighted with the diffusion's `lat` (uniform
     weights without one).  ema: an ema.EMA; sampling then runs under ema.applied(diffusion).  max_batches: stop after
-    that many batches.  RNG use is sample_ensemble's, batch after batch."""
+    that many batches.  RNG use is sample_ensemble's, batch after batch.  norm (data.load_fields' statistics): the
+    per-variable results in physical units (EnsembleVerifier.result(norm=))."""
     verifier = None
     with (ema.applied(diffusion) if ema is not None else contextlib.nullcontext()):
         for k, (cond, x0) in enumerate(loader):
@@ -191,4 +192,4 @@ def validate_ensemble(diffusion, loader, members, steps=None, ddim_eta=0.0, memb
             verifier.update(ens, x0, row0=row0)
     if verifier is None:
         raise ValueError("validate_ensemble: the loader gave no batch")
-    return verifier.result()
+    return verifier.result(norm=norm)

@@ -433,6 +433,26 @@ int cesm_cast(int dtype_in, int dtype_out, const void* x, void* y, int64_t n, hi
  * items: nitems x {t0, m, anchor, reverse, crop_i, crop_j} int64 */
 int cesm_window_gather(const float* cond, const float* tgt, const int64_t* items, float* cwin, float* x0,
                        int nitems, int K, int M, int H, int W, int h, int w, int center, hipStream_t stream);
+/* The same gather for V target variables and explicit frame indices (dataset_single_member.py:104-196: _choose_times,
+ * the crop and __getitem__; csrc/misc.hip), 1 <= V <= 4:
+ *   cond [T][M][Vc][H][W], tgt [T][M][V][H][W] fp32 (the reference's (T, M, C, H, W));
+ *   csel0 .. csel3: csel[v] in [0, Vc), by value, names the forcing plane that feeds cond channel v (entries >= V are
+ *   ignored; one forcing and two targets: Vc = 1, csel = (0, 0));
+ *   times int64 [nitems][K]: the frame indices of each item, in output order; meta int64 [nitems][4]: (member m,
+ *   anchor, crop i, crop j); both device pointers.
+ *   cwin[n][v][k][y][x] = cond[times[n][k]][m][csel[v]][i + y][j + x]     cwin [nitems][V][K][h][w]
+ *   x0[n][v][y][x]      = tgt[anchor][m][v][i + y][j + x]                 x0   [nitems][V][h][w]
+ * Time reversal and the random sample modes are a different `times` row (the host permutes it): there is no reverse or
+ * centre argument.  times and anchor are clamped into [0, T - 1], m into [0, M - 1], i into [0, H - h] and j into
+ * [0, W - w] before any address is formed, all offsets 64-bit: a bad index gives a wrong number, never a read outside
+ * the arrays.  One launch writes both outputs, one writer per element, no atomics.  16-byte stores where w % 4 == 0 and
+ * cwin, x0 are 16-byte aligned (the source start j is arbitrary: 16-byte loads only for a row that is aligned), else
+ * one element per access.  CESM_EUNSUPPORTED for V outside 1 .. 4, a csel[v] outside [0, Vc), h > H, w > W or K < 1;
+ * CESM_EINVAL on a null pointer or another size < 1.  (Added without a CESM_ABI_VERSION bump: no existing argument
+ * list changed.) */
+int cesm_window_gather_mv(const float* cond, const float* tgt, const int64_t* times, const int64_t* meta, float* cwin,
+                          float* x0, int nitems, int K, int V, int Vc, int csel0, int csel1, int csel2, int csel3,
+                          int T, int M, int H, int W, int h, int w, hipStream_t stream);
 
 #ifdef __cplusplus
 }
