@@ -188,6 +188,89 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const fl
   }
 }
 
+// DPM-Solver++(2M) step (Lu et al. 2022) from t to t_prev < t with the x0 estimate of the previous executed step at
+// t_last > t as history, per sample (Diffusion.dpmpp_coefs is the same arithmetic on the host; formulas in
+// cesm_hip.h):
+//   x_prev = a x + b eps + c x0_last,   x0 = c1 x + c2 eps
+// Thread 0 of a block forms the sample's five coefficients in double from the fp32 table (log and expm1 included),
+// rounds each to fp32 once and hands them to the block through LDS; the update itself is fp32.  Every table index is
+// clamped into 0 … T-1 before it is used (a wrong device index gives a wrong number, never a read outside the table);
+// t_prev < 0 (last step: x_prev is the x0 estimate, c = 0) and t_last < 0 (no history: the DDIM step) keep their
+// meaning.  x0_last is read only for samples with history (t_prev >= 0 and t_last >= 0) and may be null when none has.
+// blockIdx.y = sample; VEC as in ddim_step_kernel.  out may alias x and x0_out may alias x0_last (each thread reads its
+// elements before it writes them), so none of the four carries __restrict__.
+__device__ __forceinline__ int64_t clamp_i64(int64_t v, int64_t hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const float* __restrict__ eps,
+                                                         const float* x0_last, const int64_t* __restrict__ t,
+                                                         const int64_t* __restrict__ tprev,
+                                                         const int64_t* __restrict__ tlast,
+                                                         const float* __restrict__ acp, float* out, float* x0_out,
+                                                         int64_t HW, int T) {
+  __shared__ float coef[5];
+  const int b = blockIdx.y;
+  const int64_t tp = tprev[b], tl = tlast[b];
+  const bool hist = x0_last != nullptr && tp >= 0 && tl >= 0;
+  if (threadIdx.x == 0) {
+    const double ac = (double)acp[clamp_i64(t[b], T - 1)];
+    const double al_t = sqrt(ac), sg_t = sqrt(1.0 - ac), lam_t = 0.5 * log(ac / (1.0 - ac));
+    const double c1 = 1.0 / al_t, c2 = -sg_t / al_t;
+    double a = c1, bb = c2, c = 0.0;
+    if (tp >= 0) {
+      const double ap = (double)acp[clamp_i64(tp, T - 1)];
+      const double al_p = sqrt(ap), sg_p = sqrt(1.0 - ap), lam_p = 0.5 * log(ap / (1.0 - ap));
+      const double h = lam_p - lam_t;
+      const double G = -al_p * expm1(-h);
+      double wc = 1.0, wp = 0.0;
+      if (tl >= 0) {
+        const double al = (double)acp[clamp_i64(tl, T - 1)];
+        const double r = (lam_t - 0.5 * log(al / (1.0 - al))) / h;
+        wc = 1.0 + 1.0 / (2.0 * r);
+        wp = -1.0 / (2.0 * r);
+      }
+      a = sg_p / sg_t + G * wc / al_t;
+      bb = -G * wc * sg_t / al_t;
+      c = G * wp;
+    }
+    coef[0] = (float)a, coef[1] = (float)bb, coef[2] = (float)c, coef[3] = (float)c1, coef[4] = (float)c2;
+  }
+  __syncthreads();
+  const float ca = coef[0], cb = coef[1], cc = coef[2], c1 = coef[3], c2 = coef[4];
+  const int64_t base = (int64_t)b * HW;
+  x += base, eps += base, out += base, x0_out += base;
+  if (hist) x0_last += base;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (VEC) {
+    const int64_t nv = HW >> 2;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < nv; e += stride) {
+      float xv[4], ev[4], m[4], p[4];
+      load4(x + e * 4, xv);
+      load4(eps + e * 4, ev);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) m[i] = ca * xv[i] + cb * ev[i];
+      if (hist) {
+        float hv[4];
+        load4(x0_last + e * 4, hv);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) m[i] += cc * hv[i];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) p[i] = c1 * xv[i] + c2 * ev[i];
+      store4(out + e * 4, m);
+      store4(x0_out + e * 4, p);
+    }
+  } else {
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < HW; e += stride) {
+      const float xv = x[e], ev = eps[e];
+      float m = ca * xv + cb * ev;
+      if (hist) m += cc * x0_last[e];
+      out[e] = m;
+      x0_out[e] = c1 * xv + c2 * ev;
+    }
+  }
+}
+
 // loss partials: part[blk] = sum (pred - noise)^2
 __global__ void mse_partial_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                    float* __restrict__ part, int64_t n) {
@@ -592,8 +675,6 @@ struct GatherSel {
   int c0, c1, c2, c3;  // csel[v]: by value, picked with compares (no indexed private array, so no scratch)
 };
 
-__device__ __forceinline__ int64_t clamp_i64(int64_t v, int64_t hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 // q = a / b for a >= 0, b > 0: 32-bit division where a fits (every realistic row count), 64-bit otherwise
 __device__ __forceinline__ int64_t row_div(int64_t a, int b) {
   return (a >> 31) == 0 ? (int64_t)((uint32_t)a / (uint32_t)b) : a / b;
@@ -738,6 +819,25 @@ int cesm_ddim_step(const float* x, const float* eps, const float* z, const int64
     ddim_step_kernel<true><<<grid, 256, 0, stream>>>(x, eps, z, t, t_prev, alphas_cumprod, eta, out, HW);
   else
     ddim_step_kernel<false><<<grid, 256, 0, stream>>>(x, eps, z, t, t_prev, alphas_cumprod, eta, out, HW);
+  return cesm_launch_status();
+}
+
+int cesm_dpmpp_step(const float* x, const float* eps, const float* x0_last, const int64_t* t, const int64_t* t_prev,
+                    const int64_t* t_last, const float* alphas_cumprod, float* out, float* x0_out, int B, int64_t HW,
+                    int T, hipStream_t stream) {
+  if (!x || !eps || !t || !t_prev || !t_last || !alphas_cumprod || !out || !x0_out) return CESM_EINVAL;
+  if (B < 1 || B > 65535 || HW < 1 || T < 1) return CESM_EINVAL;
+  const bool vec = HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)eps | (uintptr_t)x0_last | (uintptr_t)out |
+                                    (uintptr_t)x0_out) & 15) == 0;
+  // the grid of cesm_ddim_step: about 4096 blocks over the batch, grid-stride inside a sample
+  const int64_t per = std::max<int64_t>(1, 4096 / B);
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv(vec ? HW / 4 : HW, 256), per), (unsigned)B);
+  if (vec)
+    dpmpp_step_kernel<true><<<grid, 256, 0, stream>>>(x, eps, x0_last, t, t_prev, t_last, alphas_cumprod, out, x0_out,
+                                                      HW, T);
+  else
+    dpmpp_step_kernel<false><<<grid, 256, 0, stream>>>(x, eps, x0_last, t, t_prev, t_last, alphas_cumprod, out, x0_out,
+                                                       HW, T);
   return cesm_launch_status();
 }
 

@@ -867,6 +867,35 @@ def ddim_step(x, eps, z, t, t_prev, alphas_cumprod, eta, out=None):
     return out
 
 
+def dpmpp_step(x, eps, x0_last, t, t_prev, t_last, alphas_cumprod, out=None, x0_out=None):
+    """Fused DPM-Solver++(2M) update (cesm_dpmpp_step; coefficients: Diffusion.dpmpp_coefs): returns (x_prev, x0).
+    t, t_prev, t_last [B] int64 device tensors with -1 <= t_prev < t < T and t_last = -1 (no history) or
+    t < t_last < T (the caller's range check; the kernel only clamps its table indices).  x0_last=None: no sample has
+    history; with it, only the samples with t_prev >= 0 and t_last >= 0 read it.  out may be x, x0_out may be x0_last."""
+    B = x.shape[0]
+    _chk(x, dtype=torch.float32)
+    _chk(eps, x.shape, torch.float32)
+    if x0_last is not None:
+        _chk(x0_last, x.shape, torch.float32)
+    _chk(t, (B,), torch.int64)
+    _chk(t_prev, (B,), torch.int64)
+    _chk(t_last, (B,), torch.int64)
+    _chk(alphas_cumprod, dtype=torch.float32)
+    if alphas_cumprod.ndim != 1:
+        raise RuntimeError("alphas_cumprod must be 1-D")
+    if out is None:
+        out = empty(x.shape, torch.float32, x.device)
+    else:
+        _chk(out, x.shape, torch.float32)
+    if x0_out is None:
+        x0_out = empty(x.shape, torch.float32, x.device)
+    else:
+        _chk(x0_out, x.shape, torch.float32)
+    call("cesm_dpmpp_step", P(x), P(eps), P(x0_last), P(t), P(t_prev), P(t_last), P(alphas_cumprod), P(out), P(x0_out),
+         B, x.numel() // B, alphas_cumprod.numel(), S())
+    return out, x0_out
+
+
 def mse(pred, tgt):
     loss = empty((), torch.float32, pred.device)
     part = empty((512,), torch.float32, pred.device)

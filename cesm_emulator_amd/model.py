@@ -288,16 +288,44 @@ class Diffusion(nn.Module):
                 noise = torch.randn_like(x_t)
             return K.ddpm_step(x_t, eps, noise.float().contiguous(), t, *self._coefs())
 
-    def sample_schedule(self, steps):
+    def sample_schedule(self, steps, spacing="uniform"):
         """The `steps` time indices tau of a strided sampling run: an increasing sub-sequence of 0 … T-1 that ends at
-        T-1 and (for steps >= 2) starts at 0, tau_i = round(i (T-1) / (steps-1)) in exact integer arithmetic (halves
-        round up).  Sampling walks it from the back; the t_prev of tau_0 is -1."""
+        T-1 and (for steps >= 2) starts at 0.  Sampling walks it from the back; the t_prev of tau_0 is -1.
+
+        spacing="uniform": tau_i = round(i (T-1) / (steps-1)) in exact integer arithmetic (halves round up).
+        spacing="logsnr": uniform in lambda_t = log(ac_t / (1 - ac_t)) / 2 (float64 from the fp32 alphas_cumprod):
+        tau_i is the index whose lambda is nearest lambda_0 + i (lambda_{T-1} - lambda_0) / (steps-1), ties to the
+        smaller index; then tau_0 = 0 and tau_last = T-1 are set and one forward pass (tau_i >= tau_{i-1} + 1) and one
+        backward pass from T-1 (tau_i <= tau_{i+1} - 1) make the sequence strictly increasing for every steps <= T.
+        The multistep solver needs this grid: on the uniform one its penultimate step spans most of the log-SNR range
+        and the extrapolation overshoots."""
         steps, T = int(steps), self.T
+        if spacing not in ("uniform", "logsnr"):
+            raise ValueError(f"spacing must be 'uniform' or 'logsnr', got {spacing!r}")
         if not 1 <= steps <= T:
             raise ValueError(f"steps must be in 1 … T = {T}, got {steps}")
         if steps == 1:
             return [T - 1]
-        return [(2 * i * (T - 1) + (steps - 1)) // (2 * (steps - 1)) for i in range(steps)]
+        if spacing == "uniform":
+            return [(2 * i * (T - 1) + (steps - 1)) // (2 * (steps - 1)) for i in range(steps)]
+        lam = self._lambda(self.alphas_cumprod.detach().cpu())
+        l0, l1 = lam[0].item(), lam[-1].item()
+        target = torch.tensor([l0 + i * (l1 - l0) / (steps - 1) for i in range(steps)], dtype=torch.float64)
+        # argmin returns the first of equal minima: ties go to the smaller index
+        tau = torch.argmin((lam[None, :] - target[:, None]).abs(), dim=1).tolist()
+        tau[0], tau[-1] = 0, T - 1
+        for i in range(1, steps):
+            tau[i] = max(tau[i], tau[i - 1] + 1)
+        tau[-1] = T - 1
+        for i in range(steps - 2, -1, -1):
+            tau[i] = min(tau[i], tau[i + 1] - 1)
+        return tau
+
+    @staticmethod
+    def _lambda(ac):
+        """half log-SNR lambda = log(ac / (1 - ac)) / 2 in float64 from fp32 alphas_cumprod entries"""
+        ac = ac.double()
+        return 0.5 * torch.log(ac / (1.0 - ac))
 
     def _ddim_args(self, t, t_prev, eta):
         """t, t_prev as broadcast int64 tensors on the schedule's device and eta as a float, range-checked (the update
@@ -346,8 +374,93 @@ class Diffusion(nn.Module):
                 z = (torch.randn_like(x_t) if noise is None else noise.to(x_t.device)).float().contiguous()
             return K.ddim_step(x_t, eps, z, t, t_prev, self.alphas_cumprod, eta)
 
+    def _dpmpp_args(self, t, t_prev, t_last):
+        """t, t_prev, t_last as broadcast int64 tensors on the schedule's device, range-checked (the update kernel only
+        clamps its table indices): -1 <= t_prev < t < T and t_last == -1 (no history) or t < t_last < T"""
+        dev = self.alphas_cumprod.device
+        t, t_prev, t_last = torch.broadcast_tensors(*(torch.as_tensor(v, device=dev).long()
+                                                      for v in (t, t_prev, t_last)))
+        bad = (t < 0) | (t >= self.T) | (t_prev < -1) | (t_prev >= t) | ((t_last != -1) & ((t_last <= t) |
+                                                                                            (t_last >= self.T)))
+        if bool(bad.any()):
+            raise ValueError(f"DPM-Solver++ step needs -1 <= t_prev < t < T = {self.T} and t_last = -1 or "
+                             f"t < t_last < T, got t = {t.tolist()}, t_prev = {t_prev.tolist()}, "
+                             f"t_last = {t_last.tolist()}")
+        return t.contiguous(), t_prev.contiguous(), t_last.contiguous()
+
+    def dpmpp_coefs(self, t, t_prev, t_last):
+        """(a, b, c, c1, c2) of the DPM-Solver++(2M) step (Lu et al. 2022) from t to t_prev < t,
+            x_prev = a x_t + b eps + c x0_last,   x0 = c1 x_t + c2 eps,
+        as float64 tensors of the broadcast shape; t, t_prev, t_last: ints or integer tensors.  x0 is this step's data
+        prediction (the next step's history), x0_last the one of the previous executed step, taken at t_last > t;
+        t_last = -1: no history.  With alpha_u = sqrt(ac_u), sigma_u = sqrt(1 - ac_u) and
+        lambda_u = log(ac_u / (1 - ac_u)) / 2 in float64 from the fp32 alphas_cumprod entries:
+            c1 = 1 / alpha_t,  c2 = -sigma_t / alpha_t;
+            t_prev >= 0:  h = lambda_prev - lambda_t,  G = -alpha_prev expm1(-h),
+                          w_c = 1, w_p = 0 without history, else r = (lambda_t - lambda_last) / h,
+                          w_c = 1 + 1 / (2 r), w_p = -1 / (2 r);
+                          a = sigma_prev / sigma_t + G w_c / alpha_t,  b = -G w_c sigma_t / alpha_t,  c = G w_p;
+            t_prev = -1 (the last step: returns the x0 estimate, never extrapolates):  a = c1, b = c2, c = 0.
+        Without history the step is the DDIM step at eta = 0.  The update kernel (csrc/misc.hip dpmpp_step_kernel) does
+        the same arithmetic and rounds each of the five to fp32 once."""
+        t, t_prev, t_last = self._dpmpp_args(t, t_prev, t_last)
+        ac = self.alphas_cumprod
+        at, ap, al = ac[t].double(), ac[t_prev.clamp_min(0)].double(), ac[t_last.clamp_min(0)].double()
+        alpha_t, sigma_t, lam_t = at.sqrt(), (1.0 - at).sqrt(), self._lambda(at)
+        c1, c2 = 1.0 / alpha_t, -sigma_t / alpha_t
+        h = self._lambda(ap) - lam_t
+        G = -ap.sqrt() * torch.expm1(-h)
+        r = (lam_t - self._lambda(al)) / h
+        hist = t_last >= 0
+        w_c = torch.where(hist, 1.0 + 1.0 / (2.0 * r), torch.ones_like(r))
+        w_p = torch.where(hist, -1.0 / (2.0 * r), torch.zeros_like(r))
+        last = t_prev < 0
+        a = torch.where(last, c1, (1.0 - ap).sqrt() / sigma_t + G * w_c / alpha_t)
+        b = torch.where(last, c2, -G * w_c * sigma_t / alpha_t)
+        c = torch.where(last, torch.zeros_like(G), G * w_p)
+        return a, b, c, c1, c2
+
     @torch.no_grad()
-    def sample(self, cond, shape, device, use_graph=None, x_T=None, noise_seq=None, steps=None, ddim_eta=0.0):
+    def dpmpp_step(self, x_t, cond, t, t_prev, t_last, x0_last=None):
+        """One DPM-Solver++(2M) step t -> t_prev (per sample; dpmpp_coefs has the formula): model evaluation + one
+        fused update kernel, the eager counterpart of ddim_step.  Returns (x_prev, x0): x0 is the step's data
+        prediction, to be passed as x0_last, with this t as t_last, to the next step.  x0_last is needed where
+        t_last >= 0 and is not read elsewhere; deterministic, draws nothing."""
+        with torch.inference_mode():
+            x_t = x_t.float().contiguous()
+            B = x_t.shape[0]
+            t, t_prev, t_last = (v.to(x_t.device).expand(B).contiguous() for v in self._dpmpp_args(t, t_prev, t_last))
+            if x0_last is None and bool(((t_last >= 0) & (t_prev >= 0)).any()):
+                raise ValueError("dpmpp_step: t_last >= 0 needs x0_last, the previous step's x0 estimate")
+            if x0_last is not None:
+                x0_last = x0_last.to(x_t.device).float().contiguous()
+            eps = self.model(x_t, cond, t).float().contiguous()
+            return K.dpmpp_step(x_t, eps, x0_last, t, t_prev, t_last, self.alphas_cumprod)
+
+    def _sample_grid(self, steps, ddim_eta, solver, spacing):
+        """the checks of sample()'s solver arguments, before anything is captured: (tau, ddim_eta), tau = None for
+        steps=None (the ancestral loop, which has no grid: solver and spacing are only checked)"""
+        if solver not in ("ddim", "dpmpp2m"):
+            raise ValueError(f"solver must be 'ddim' or 'dpmpp2m', got {solver!r}")
+        if spacing is None:
+            spacing = "uniform" if solver == "ddim" else "logsnr"
+        if spacing not in ("uniform", "logsnr"):
+            raise ValueError(f"spacing must be 'uniform' or 'logsnr', got {spacing!r}")
+        if solver == "dpmpp2m":
+            if steps is None:
+                raise ValueError("solver='dpmpp2m' needs steps")
+            if float(ddim_eta) != 0.0:
+                raise ValueError(f"solver='dpmpp2m' is deterministic: ddim_eta must be 0, got {ddim_eta}")
+        if steps is None:
+            return None, ddim_eta
+        ddim_eta = float(ddim_eta)
+        if not ddim_eta >= 0.0:
+            raise ValueError(f"ddim_eta must be >= 0, got {ddim_eta}")
+        return self.sample_schedule(steps, spacing), ddim_eta
+
+    @torch.no_grad()
+    def sample(self, cond, shape, device, use_graph=None, x_T=None, noise_seq=None, steps=None, ddim_eta=0.0,
+               solver="ddim", spacing=None):
         """model.py:186-194.  On the GPU every p_sample step is ONE replay of a captured HIP graph (the
         F=1 network forward + the fused update); the host only sets t and draws the step noise.  RNG use
         is the reference's: randn(shape) for x_T, then randn_like(x) for every step with t > 0, drawn
@@ -359,12 +472,19 @@ class Diffusion(nn.Module):
         deterministic; > 0: stochastic, 1 on the full grid is DDPM); steps=None is the ancestral loop above whatever
         ddim_eta is.  RNG use then: randn(shape) for x_T unless given, and only for ddim_eta > 0 one randn_like per
         executed step except the last, in step order, outside the graph on the default generator; noise_seq is
-        [N, *shape] (entry k for executed step k, the last one unused).  ddim_eta = 0 with x_T draws nothing."""
-        return self._sample(cond, shape, device, use_graph, x_T, noise_seq, steps, ddim_eta, False)
+        [N, *shape] (entry k for executed step k, the last one unused).  ddim_eta = 0 with x_T draws nothing.
+
+        solver="dpmpp2m" takes the N steps with DPM-Solver++(2M) instead (dpmpp_coefs; second order: every step but
+        the first and the last also uses the previous step's x0 estimate, at no further network evaluation).  It
+        needs steps and ddim_eta == 0, is deterministic (randn(shape) for x_T unless given, nothing else; noise_seq is
+        unused), and for executed step k its t_last is the t of step k-1, -1 at k = 0.  spacing picks the time grid
+        (sample_schedule): None means "uniform" for ddim and "logsnr" for dpmpp2m; either may be given to either."""
+        return self._sample(cond, shape, device, use_graph, x_T, noise_seq, steps, ddim_eta, False, solver=solver,
+                            spacing=spacing)
 
     @torch.no_grad()
     def sample_ensemble(self, cond, members, device=None, steps=None, ddim_eta=0.0, member_batch=None, x_T=None,
-                        noise_seq=None, use_graph=None):
+                        noise_seq=None, use_graph=None, solver="ddim", spacing=None):
         """`members` samples for every row of cond: [B, M, V, H, W] fp32 (cond [B, V, H, W] or a window
         [B, V, Fc, H, W]).  The B M jobs, b-major (job b M + m is member m of cond[b]), run in chunks of at most
         member_batch network samples (default: all in one chunk); each chunk goes through sample()'s loop with
@@ -372,14 +492,15 @@ class Diffusion(nn.Module):
         On the graph path one GraphSampleStep is captured per distinct chunk size of the call (at most two: the full
         chunks and a shorter last one); later chunks of that size load their cond and x_T into its static buffers.
 
-        steps / ddim_eta / use_graph: as sample().  RNG use, chunk by chunk: randn for the chunk's x_T, then that
-        chunk's step noise exactly as sample() documents, then the next chunk.  Test hooks: x_T [B, M, V, H, W] and
+        steps / ddim_eta / use_graph / solver / spacing: as sample().  RNG use, chunk by chunk: randn for the chunk's
+        x_T, then that chunk's step noise exactly as sample() documents, then the next chunk.  Test hooks: x_T [B, M, V, H, W] and
         noise_seq [N, B, M, V, H, W] replace the draws, sliced per chunk; with them a chunk equals, bit for bit,
         sample(cond.repeat_interleave(M, 0)[chunk], ..., x_T=..., noise_seq=...) on the same rows."""
         return self._sample_ensemble(cond, members, device, steps, ddim_eta, member_batch, x_T, noise_seq, use_graph,
-                                     False)
+                                     False, solver=solver, spacing=spacing)
 
-    def _sample_ensemble(self, cond, members, device, steps, ddim_eta, member_batch, x_T, noise_seq, use_graph, paired):
+    def _sample_ensemble(self, cond, members, device, steps, ddim_eta, member_batch, x_T, noise_seq, use_graph, paired,
+                         solver="ddim", spacing=None):
         """sample_ensemble(); paired: cond is two halves [cond, cond2] whose jobs b M + m get the same x_T and step
         noise (one chunk only: counterfactual_delta)"""
         if cond.ndim not in (4, 5):
@@ -401,9 +522,8 @@ class Diffusion(nn.Module):
             raise ValueError(f"noise_seq must be [N, {B}, {M}, {V}, {H}, {W}], got {tuple(noise_seq.shape)}")
         if use_graph is None:
             use_graph = os.environ.get("CESM_SAMPLE_GRAPH", "1") != "0"
+        self._sample_grid(steps, ddim_eta, solver, spacing)  # range checks before anything is captured
         eta = None if steps is None else float(ddim_eta)
-        if steps is not None:
-            self.sample_schedule(steps)  # range check before anything is captured
         with torch.inference_mode():
             cond = cond.to(device)
             out = torch.empty((B, M, V, H, W), dtype=torch.float32, device=device)
@@ -420,22 +540,20 @@ class Diffusion(nn.Module):
                     step = captured.get(n)
                     if step is None:
                         step = captured[n] = GraphSampleStep(self, c, torch.zeros((n, V, H, W), device=device),
-                                                             ddim_eta=eta)
+                                                             ddim_eta=eta, solver=solver)
                 x = self._sample(c, (n, V, H, W), device, use_graph, None if xT is None else xT[j0:j1],
-                                 None if ns is None else ns[:, j0:j1], steps, ddim_eta, paired, step=step)
+                                 None if ns is None else ns[:, j0:j1], steps, ddim_eta, paired, step=step,
+                                 solver=solver, spacing=spacing)
                 flat[j0:j1].copy_(x)
             return out
 
-    def _sample(self, cond, shape, device, use_graph, x_T, noise_seq, steps, ddim_eta, paired, step=None):
+    def _sample(self, cond, shape, device, use_graph, x_T, noise_seq, steps, ddim_eta, paired, step=None,
+                solver="ddim", spacing=None):
         """sample(); paired: the batch is two halves that get the same x_T and the same step noise (drawn for one
         half, copied to the other: counterfactual_delta).  step: a GraphSampleStep captured earlier for this batch
-        size and ddim_eta (sample_ensemble); the graph path then loads cond and x_T into its static buffers instead of
-        capturing a new one, and the result is that step's x buffer (valid until the step runs again)."""
-        if steps is not None:
-            tau = self.sample_schedule(steps)
-            ddim_eta = float(ddim_eta)
-            if not ddim_eta >= 0.0:
-                raise ValueError(f"ddim_eta must be >= 0, got {ddim_eta}")
+        size, ddim_eta and solver (sample_ensemble); the graph path then loads cond and x_T into its static buffers
+        instead of capturing a new one, and the result is that step's x buffer (valid until the step runs again)."""
+        tau, ddim_eta = self._sample_grid(steps, ddim_eta, solver, spacing)
         if paired and shape[0] % 2:
             raise ValueError("paired sampling needs an even batch")
 
@@ -460,6 +578,22 @@ class Diffusion(nn.Module):
             if steps is not None:
                 # executed step k: t = tau[-1-k] -> t_prev = tau[-2-k], -1 after tau[0]
                 pairs = list(zip(reversed(tau), reversed([-1] + tau[:-1])))
+                if solver == "dpmpp2m":
+                    # the history of executed step k is step k-1's x0 estimate, taken at its t
+                    lasts = [-1] + [tt for tt, _ in pairs[:-1]]
+                    if not use_graph:
+                        x0 = None
+                        for (tt, tp), tl in zip(pairs, lasts):
+                            tt, tp, tl = (torch.full((B,), v, device=device, dtype=torch.long) for v in (tt, tp, tl))
+                            x, x0 = self.dpmpp_step(x, cond, tt, tp, tl, x0)
+                        return x
+                    if step is None:
+                        step = GraphSampleStep(self, cond, x, ddim_eta=0.0, solver=solver)
+                    else:
+                        step.load(cond, x)
+                    for (tt, tp), tl in zip(pairs, lasts):
+                        step.run(tt, tp, tl)
+                    return step.x
                 noisy = ddim_eta > 0.0
                 if not use_graph:
                     for k, (tt, tp) in enumerate(pairs):
@@ -513,10 +647,22 @@ class GraphSampleStep:
 
     ddim_eta=None is that DDPM step.  With ddim_eta >= 0 the captured update is the generalized DDIM step instead
     (Diffusion.ddim_step): t_prev [B] int64 is a further static input, run(tt, tt_prev) sets both, and z exists only
-    for ddim_eta > 0 (None at 0: the graph holds no noise buffer)."""
+    for ddim_eta > 0 (None at 0: the graph holds no noise buffer).
 
-    def __init__(self, diffusion, cond, x, ddim_eta=None):
+    solver="dpmpp2m" (ddim_eta None or 0) captures the DPM-Solver++(2M) step (Diffusion.dpmpp_step) in place on x and
+    on a static history buffer x0_last, which every replay overwrites with its x0 estimate: t_prev and t_last are
+    static inputs, run(tt, tt_prev, tt_last) sets all three, and there is no noise buffer.  A step with tt_last = -1
+    does not read the history, so load() leaves it as it is."""
+
+    def __init__(self, diffusion, cond, x, ddim_eta=None, solver="ddim"):
         self.d = diffusion
+        if solver not in ("ddim", "dpmpp2m"):
+            raise ValueError(f"solver must be 'ddim' or 'dpmpp2m', got {solver!r}")
+        self.multistep = solver == "dpmpp2m"
+        if self.multistep:
+            if ddim_eta is not None and float(ddim_eta) != 0.0:
+                raise ValueError(f"solver='dpmpp2m' is deterministic: ddim_eta must be None or 0, got {ddim_eta}")
+            ddim_eta = 0.0
         self.eta = None if ddim_eta is None else float(ddim_eta)
         if self.eta is not None and not self.eta >= 0.0:
             raise ValueError(f"ddim_eta must be >= 0, got {ddim_eta}")
@@ -524,6 +670,8 @@ class GraphSampleStep:
         self.cond = cond.float().contiguous()
         self.t = torch.zeros(x.shape[0], dtype=torch.long, device=x.device)
         self.t_prev = None if self.eta is None else torch.full_like(self.t, -1)
+        self.t_last = torch.full_like(self.t, -1) if self.multistep else None
+        self.x0_last = torch.zeros_like(self.x) if self.multistep else None
         self.z = torch.zeros_like(self.x) if self.eta is None or self.eta > 0.0 else None
         x0 = self.x.clone()
         side = torch.cuda.Stream()
@@ -550,16 +698,26 @@ class GraphSampleStep:
         eps = self.d.model(self.x, self.cond, self.t).float().contiguous()
         if self.eta is None:
             K.ddpm_step(self.x, eps, self.z, self.t, *self.d._coefs(), out=self.x)
+        elif self.multistep:
+            K.dpmpp_step(self.x, eps, self.x0_last, self.t, self.t_prev, self.t_last, self.d.alphas_cumprod, out=self.x,
+                         x0_out=self.x0_last)
         else:
             K.ddim_step(self.x, eps, self.z, self.t, self.t_prev, self.d.alphas_cumprod, self.eta, out=self.x)
 
-    def run(self, tt, tt_prev=None):
-        """one step at time index tt for every sample; a DDIM step also needs its target tt_prev (-1 <= tt_prev < tt)"""
+    def run(self, tt, tt_prev=None, tt_last=None):
+        """one step at time index tt for every sample; a DDIM step also needs its target tt_prev (-1 <= tt_prev < tt),
+        a DPM-Solver++(2M) step also the previous step's time index tt_last (-1: none, else tt < tt_last < T)"""
         if (tt_prev is None) != (self.t_prev is None):
             raise ValueError("run(tt) is the DDPM step, run(tt, tt_prev) the DDIM step (ddim_eta given)")
+        if (tt_last is None) != (self.t_last is None):
+            raise ValueError("run(tt, tt_prev, tt_last) is the DPM-Solver++(2M) step (solver='dpmpp2m')")
         if not 0 <= tt < self.d.T or (tt_prev is not None and not -1 <= tt_prev < tt):
             raise ValueError(f"step indices out of range: t = {tt}, t_prev = {tt_prev}, T = {self.d.T}")
+        if tt_last is not None and not (tt_last == -1 or tt < tt_last < self.d.T):
+            raise ValueError(f"step indices out of range: t = {tt}, t_last = {tt_last}, T = {self.d.T}")
         self.t.fill_(tt)
         if tt_prev is not None:
             self.t_prev.fill_(tt_prev)
+        if tt_last is not None:
+            self.t_last.fill_(tt_last)
         self.graph.replay()

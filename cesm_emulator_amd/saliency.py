@@ -34,10 +34,10 @@ def input_grads(diffusion, x0, cond, t=None, noise=None):
 
 
 def counterfactual_delta(diffusion, cond, scale_mask=None, scale=1.1, steps=None, ddim_eta=0.0, paired=False,
-                         n_samples=1):
+                         n_samples=1, solver="ddim", spacing=None):
     """Sampled response to scaled emissions (the reference's train.py counterfactual_delta): sample(cond2) -
-    sample(cond) with cond2 = cond * scale, or cond * (1 + (scale - 1) * scale_mask) where a mask is given.  steps and
-    ddim_eta go to Diffusion.sample (steps=None: the full ancestral loop).
+    sample(cond) with cond2 = cond * scale, or cond * (1 + (scale - 1) * scale_mask) where a mask is given.  steps,
+    ddim_eta, solver and spacing go to Diffusion.sample (steps=None: the full ancestral loop).
 
     Default: two sampling runs, base first, each drawing its own x_T and step noise (the reference's semantics), so
     the difference also carries the sampling noise.  paired=True: ONE run of batch 2B over [cond, cond2] in which both
@@ -53,20 +53,21 @@ def counterfactual_delta(diffusion, cond, scale_mask=None, scale=1.1, steps=None
         raise ValueError(f"n_samples must be >= 1, got {n_samples}")
     cond2 = cond * scale if scale_mask is None else cond * (1.0 + (scale - 1.0) * scale_mask)
     B, V, H, W = cond.shape[0], cond.shape[1], cond.shape[-2], cond.shape[-1]  # V target variables, as cond has
+    kw = dict(solver=solver, spacing=spacing)
     if n_samples > 1:
         if paired:
             x = diffusion._sample_ensemble(torch.cat([cond, cond2], dim=0), n_samples, cond.device, steps, ddim_eta,
-                                           None, None, None, None, True)
+                                           None, None, None, None, True, **kw)
             return x[B:].mean(dim=1) - x[:B].mean(dim=1)
-        base = diffusion.sample_ensemble(cond, n_samples, steps=steps, ddim_eta=ddim_eta).mean(dim=1)
-        pert = diffusion.sample_ensemble(cond2, n_samples, steps=steps, ddim_eta=ddim_eta).mean(dim=1)
+        base = diffusion.sample_ensemble(cond, n_samples, steps=steps, ddim_eta=ddim_eta, **kw).mean(dim=1)
+        pert = diffusion.sample_ensemble(cond2, n_samples, steps=steps, ddim_eta=ddim_eta, **kw).mean(dim=1)
         return pert - base
     if paired:
         x = diffusion._sample(torch.cat([cond, cond2], dim=0), (2 * B, V, H, W), cond.device, None, None, None, steps,
-                              ddim_eta, True)
+                              ddim_eta, True, **kw)
         return x[B:] - x[:B]
-    base = diffusion.sample(cond, (B, V, H, W), cond.device, steps=steps, ddim_eta=ddim_eta)
-    pert = diffusion.sample(cond2, (B, V, H, W), cond.device, steps=steps, ddim_eta=ddim_eta)
+    base = diffusion.sample(cond, (B, V, H, W), cond.device, steps=steps, ddim_eta=ddim_eta, **kw)
+    pert = diffusion.sample(cond2, (B, V, H, W), cond.device, steps=steps, ddim_eta=ddim_eta, **kw)
     return pert - base
 
 

@@ -169,10 +169,10 @@ def train_one_epoch(diffusion, dl, optimizer, device, max_grad_norm=1.0, use_amp
 
 
 def validate_ensemble(diffusion, loader, members, steps=None, ddim_eta=0.0, member_batch=None, max_batches=None,
-                      ema=None, norm=None):
+                      ema=None, norm=None, solver="ddim", spacing=None):
     """Ensemble verification over a loader of (cond, target) batches: per batch, `members` samples per condition
-    (Diffusion.sample_ensemble with steps / ddim_eta / member_batch) are judged against the loader's target with the
-    batch's crop row offsets (`loader.last_row0`; a loader without it: no crop), all batches accumulated on the device
+    (Diffusion.sample_ensemble with steps / ddim_eta / member_batch / solver / spacing) are judged against the loader's
+    target with the batch's crop row offsets (`loader.last_row0`; a loader without it: no crop), all batches accumulated on the device
     (ensemble.EnsembleVerifier, one kernel call per batch, no host synchronisation).  Returns the verifier's result():
     per-variable mse, rmse, var, spread, ssr, crps and rank_hist, area-weighted with the diffusion's `lat` (uniform
     weights without one).  ema: an ema.EMA; sampling then runs under ema.applied(diffusion).  max_batches: stop after
@@ -188,7 +188,8 @@ def validate_ensemble(diffusion, loader, members, steps=None, ddim_eta=0.0, memb
             cond, x0 = cond.to(device), x0.to(device).float().contiguous()
             if verifier is None:
                 verifier = EnsembleVerifier(members, x0.shape[1], lat=diffusion._lat, device=device)
-            ens = diffusion.sample_ensemble(cond, members, steps=steps, ddim_eta=ddim_eta, member_batch=member_batch)
+            ens = diffusion.sample_ensemble(cond, members, steps=steps, ddim_eta=ddim_eta, member_batch=member_batch,
+                                            solver=solver, spacing=spacing)
             verifier.update(ens, x0, row0=row0)
     if verifier is None:
         raise ValueError("validate_ensemble: the loader gave no batch")

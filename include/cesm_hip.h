@@ -352,6 +352,28 @@ int cesm_ddpm_step(const float* x, const float* eps, const float* z, const int64
  * An added entry point (no existing argument list changed): the ABI version stays, as for cesm_stem_dgrad. */
 int cesm_ddim_step(const float* x, const float* eps, const float* z, const int64_t* t, const int64_t* t_prev,
                    const float* alphas_cumprod, float eta, float* out, int B, int64_t HW, int T, hipStream_t stream);
+/* Diffusion.dpmpp_step update: one DPM-Solver++(2M) step (Lu et al. 2022) from t to t_prev < t, with the x0 estimate
+ * of the previous executed step (at t_last > t) as history, fused:
+ *   out = a x + b eps + c x0_last,   x0_out = c1 x + c2 eps.
+ * With ac_u = alphas_cumprod[u], alpha_u = sqrt(ac_u), sigma_u = sqrt(1 - ac_u), lambda_u = log(ac_u / (1 - ac_u)) / 2,
+ * formed per sample on the device in double (log and expm1 too) and rounded to fp32 once each -- the arithmetic of
+ * Diffusion.dpmpp_coefs:
+ *   c1 = 1 / alpha_t,  c2 = -sigma_t / alpha_t                        (the x0 estimate)
+ *   t_prev >= 0:  h = lambda_prev - lambda_t,  G = -alpha_prev expm1(-h),
+ *                 t_last < 0 (no history):  w_c = 1, w_p = 0          (the DDIM step at eta = 0)
+ *                 t_last >= 0:  r = (lambda_t - lambda_last) / h,  w_c = 1 + 1/(2r),  w_p = -1/(2r)
+ *                 a = sigma_prev / sigma_t + G w_c / alpha_t,  b = -G w_c sigma_t / alpha_t,  c = G w_p
+ *   t_prev < 0 (last step, returns the x0 estimate, never extrapolates):  a = c1, b = c2, c = 0.
+ * t, t_prev, t_last: [B] device tensors, -1 <= t_prev[b] < t[b] < T and t_last[b] = -1 or t[b] < t_last[b] < T (the
+ * caller's check); every table index formed from them is clamped into 0 ... T-1 here, so a wrong index gives a wrong
+ * number, not a read outside the table.  x0_last is read only for samples with t_prev >= 0 and t_last >= 0 and may be
+ * NULL when no sample has history.  out may alias x and x0_out may alias x0_last.  x, eps, x0_last, out, x0_out:
+ * [B][HW] fp32; alphas_cumprod: [T] fp32.  16-byte accesses where HW % 4 == 0 and all five are 16-byte aligned, else
+ * one element per access.  CESM_EINVAL on a null pointer (x0_last apart), B < 1, B > 65535, HW < 1 or T < 1.
+ * An added entry point (no existing argument list changed): the ABI version stays, as for cesm_ddim_step. */
+int cesm_dpmpp_step(const float* x, const float* eps, const float* x0_last, const int64_t* t, const int64_t* t_prev,
+                    const int64_t* t_last, const float* alphas_cumprod, float* out, float* x0_out, int B, int64_t HW,
+                    int T, hipStream_t stream);
 int cesm_mse(const float* pred, const float* tgt, float* loss, float* part, int64_t n, hipStream_t stream);
 int cesm_mse_bwd(const float* pred, const float* tgt, const float* gscale, float* dpred, int64_t n,
                  hipStream_t stream);
