@@ -1,4 +1,5 @@
-// Channel LayerNorm, forward and backward (GroupNorm lives in gn.hip).
+// Channel LayerNorm, forward and backward (GroupNorm lives in gn.hip), and through tconv.h the temporal-conv blocks of
+// UNet(use_temp_attn=False), whose fp32 path reuses the LayerNorm kernels.
 //
 // GroupNorm: video_net.py:216-227 (Block: GroupNorm(8, C) eps 1e-5 affine -> x*(scale+1)+shift
 // -> SiLU) and :265 (ResnetBlock residual add, fused into the apply pass).  Statistics are per
@@ -132,6 +133,8 @@ static int dispatch_dt(int dtype, F&& f) {
 
 }  // namespace
 
+#include "tconv.h"
+
 extern "C" {
 
 // x,out: [V][C]; mr: [V][2] (mean, rstd) saved for backward (may be null).  perm_f > 0: V = B * perm_f * perm_hw
@@ -164,6 +167,21 @@ int cesm_ln_bwd(int dtype, const void* dy, const void* x, const float* mr, const
   if (rc) return rc;
   if (dgamma) sum_rows_kernel<<<C, 64, 0, stream>>>(part, dgamma, nblk, C, accumulate);
   return cesm_launch_status();
+}
+
+// ---- temporal-convolution blocks (kernels and launchers: tconv.h)
+int cesm_tconv_supported(int C) { return C == 64 || C == 128 || C == 256; }
+int64_t cesm_tconv_part_floats(int dtype, int B, int F, int HW, int C) { return tconv_part_floats(dtype, B, F, HW, C); }
+int64_t cesm_tconv_slab_floats(int dtype, int B, int F, int HW, int C) { return tconv_slab_floats(dtype, B, F, HW, C); }
+int cesm_tconv_fwd(int dtype, const void* x, const float* gamma, const void* wp, const float* bias, void* y, float* mr,
+                   void* ws, int B, int F, int HW, int C, float eps, hipStream_t stream) {
+  return tconv_fwd_launch(dtype, x, gamma, wp, bias, y, mr, ws, B, F, HW, C, eps, stream);
+}
+int cesm_tconv_bwd(int dtype, const void* x, const void* dy, const float* mr, const float* gamma, const void* wpt, void* dx,
+                   float* dgamma, float* dw, float* db, float* part, float* slab, void* ws_n, void* ws_dn, int B, int F,
+                   int HW, int C, float eps, int accumulate, hipStream_t stream) {
+  return tconv_bwd_launch(dtype, x, dy, mr, gamma, wpt, dx, dgamma, dw, db, part, slab, ws_n, ws_dn, B, F, HW, C, eps,
+                          accumulate, stream);
 }
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 
 Counts every multiply-accumulate of the dense contractions: convs (stem, 3x3, 1x1 res, 4x4 down,
 4x4 transposed up), attention projections (to_qkv / to_out), the temporal-attention core (q.k and
-attn.v: 2*F*32 per query per head) and the spatial-linear-attention core (context k.v^T and
+attn.v: 2*F*32 per query per head; a temporal-conv block of use_temp_attn=False: 3*C*C per voxel
+instead) and the spatial-linear-attention core (context k.v^T and
 context^T.q: 2*32*32 per position per head).  Training FLOPs/sample = 3 * 2 * forward MACs
 (fwd + dgrad + wgrad), the convention of SURVEY.md §8(d) D4.  The head conv is counted on every
 frame although only frame F//2 is evaluated (64 MAC/voxel, < 0.01 %).
@@ -35,8 +36,11 @@ def unet_forward_macs(net, F, H, W):
         return m
 
     def tattn(res_mod, hh, ww):
-        a = res_mod.fn.fn.fn
         v = F * hh * ww
+        if hasattr(res_mod.fn.fn, "temporal_conv"):  # use_temp_attn=False: a 3-tap conv over frames, 3 C^2 per voxel
+            wt = res_mod.fn.fn.temporal_conv.weight
+            return v * wt.shape[0] * wt.shape[1] * wt.shape[2]
+        a = res_mod.fn.fn.fn
         d = a.to_qkv.in_features
         return v * (768 * d + 256 * d) + v * 8 * 2 * F * 32
 

@@ -480,6 +480,63 @@ def ln_bwd(dy, x, mr, gamma, dgamma, dres=None, perm=None):
     return dx
 
 
+TCONV_C = (64, 128, 256)  # widths of the temporal-convolution kernels (csrc/tconv.h)
+
+
+def tconv_fwd(x, gamma, wp, bias, B, F, save=True, eps=1e-5):
+    """Residual(PreNorm(TemporalCNN)) forward (csrc/tconv.h): x [B*F, H, W, C]; wp = conv_pack(w, x.dtype, C, C, 1, 3, 0, 0)
+    of the Conv1d weight [C, C, 3]; returns (y, mr) with mr [V, 2] = (mean, rstd) per voxel when save, else None."""
+    Nb, H, W, C = x.shape
+    if C not in TCONV_C:
+        raise ValueError(f"tconv_fwd: C = {C} is not one of {TCONV_C}")
+    if Nb != B * F:
+        raise RuntimeError(f"tconv_fwd: {Nb} images are not B x F = {B} x {F}")
+    _chk(x)
+    _chk(wp, (C, 3 * C), x.dtype)
+    _chk(gamma, (C,), torch.float32)
+    _chk(bias, (C,), torch.float32)
+    V = Nb * H * W
+    y = empty(x.shape, x.dtype, x.device)
+    mr = empty((V, 2), torch.float32, x.device) if save else None
+    ws = empty(x.shape, x.dtype, x.device) if x.dtype == torch.float32 else None
+    call("cesm_tconv_fwd", dtcode(x), P(x), P(gamma), P(wp), P(bias), P(y), P(mr), P(ws), B, F, H * W, C, float(eps), S())
+    return y, mr
+
+
+def tconv_bwd(x, dy, mr, gamma, wpt, dgamma, dw, db, B, F, eps=1e-5, accumulate=True):
+    """backward of tconv_fwd: returns dx; dgamma [C], dw [C, C, 3], db [C] fp32 (+)= their gradients, each nullable (then
+    not computed).  wpt = conv_pack(w, x.dtype, C, C, 1, 3, 1, 1)."""
+    Nb, H, W, C = x.shape
+    if C not in TCONV_C:
+        raise ValueError(f"tconv_bwd: C = {C} is not one of {TCONV_C}")
+    if Nb != B * F:
+        raise RuntimeError(f"tconv_bwd: {Nb} images are not B x F = {B} x {F}")
+    V = Nb * H * W
+    _chk(x)
+    _chk(dy, x.shape, x.dtype)
+    _chk(mr, (V, 2), torch.float32)
+    _chk(wpt, (C, 3 * C), x.dtype)
+    _chk(gamma, (C,), torch.float32)
+    _chk(dgamma, (C,), torch.float32)
+    _chk(dw, (C, C, 3), torch.float32)
+    _chk(db, (C,), torch.float32)
+    dev, f32 = x.device, x.dtype == torch.float32
+    dt = dtcode(x)
+    dx = empty(x.shape, x.dtype, dev)
+    part = slab = ws_n = ws_dn = None
+    if f32 or dgamma is not None or db is not None:
+        part = empty((lib().cesm_tconv_part_floats(dt, B, F, H * W, C),), torch.float32, dev)
+    if dw is not None:
+        slab = empty((lib().cesm_tconv_slab_floats(dt, B, F, H * W, C),), torch.float32, dev)
+    if f32:
+        ws_dn = empty(x.shape, x.dtype, dev)
+        if dw is not None or db is not None:
+            ws_n = empty(x.shape, x.dtype, dev)
+    call("cesm_tconv_bwd", dt, P(x), P(dy), P(mr), P(gamma), P(wpt), P(dx), P(dgamma), P(dw), P(db), P(part), P(slab),
+         P(ws_n), P(ws_dn), B, F, H * W, C, float(eps), int(accumulate), S())
+    return dx
+
+
 def add(a, b):
     out = empty(a.shape, a.dtype, a.device)
     _chk(b, a.shape, a.dtype)

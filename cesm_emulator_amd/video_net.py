@@ -344,6 +344,19 @@ class Attention(nn.Module):
         self.to_out = nn.Linear(dim_head * heads, dim, bias=False)
 
 
+class TemporalCNN(nn.Module):
+    """video_net.py:457-483 -- Conv1d(dim, dim, 3, padding=1) over the frame axis, initialised to the identity."""
+
+    def __init__(self, dim):
+        super().__init__()
+        if dim not in K.TCONV_C:
+            raise NotImplementedError(f"temporal-conv blocks are built for widths {K.TCONV_C} (the kernels of "
+                                      f"csrc/tconv.h), got {dim}")
+        self.temporal_conv = nn.Conv1d(dim, dim, 3, padding=1)  # drawn first (the reference's RNG order), then overwritten
+        nn.init.dirac_(self.temporal_conv.weight.data)
+        nn.init.zeros_(self.temporal_conv.bias.data)
+
+
 class SpatialLinearAttention(nn.Module):
     def __init__(self, dim, heads=8, dim_head=32):
         super().__init__()
@@ -618,6 +631,35 @@ def tattn_bwd(rc, res_mod, st, dy):
     return K.ln_bwd(dn, st.x, st.mr, _flat(pre.norm.gamma), gbuf(pre.norm.gamma), dres=dy, perm=st.perm)
 
 
+def tconv_fwd(rc, res_mod, x):
+    """Residual(PreNorm(TemporalCNN)) (video_net.py:457-483): one kernel (csrc/tconv.h); the tape keeps x and the
+    per-voxel (mean, rstd) -- the normalised tensor is recomputed in the backward."""
+    pre = res_mod.fn
+    conv = pre.fn.temporal_conv
+    C = x.shape[-1]
+    wp = rc.packed(conv.weight, C, C, 1, 3, 0, 0)
+    y, mr = K.tconv_fwd(x, _flat(pre.norm.gamma), wp, conv.bias, rc.B, rc.F, save=rc.save, eps=pre.norm.eps)
+    return y, (SimpleNamespace(x=x, mr=mr) if rc.save else None)
+
+
+def tconv_bwd(rc, res_mod, st, dy):
+    pre = res_mod.fn
+    conv = pre.fn.temporal_conv
+    C = st.x.shape[-1]
+    wpt = rc.packed(conv.weight, C, C, 1, 3, 1, 1)
+    return K.tconv_bwd(st.x, dy, st.mr, _flat(pre.norm.gamma), wpt, _gflat(pre.norm.gamma), gbuf(conv.weight),
+                       gbuf(conv.bias), rc.B, rc.F, eps=pre.norm.eps)
+
+
+def temporal_fwd(rc, res_mod, x):
+    """the temporal op of a level: attention or, with use_temp_attn=False on the shallow levels, the temporal conv"""
+    return (tconv_fwd if isinstance(res_mod.fn.fn, TemporalCNN) else tattn_fwd)(rc, res_mod, x)
+
+
+def temporal_bwd(rc, res_mod, st, dy):
+    return (tconv_bwd if isinstance(res_mod.fn.fn, TemporalCNN) else tattn_bwd)(rc, res_mod, st, dy)
+
+
 def _sla_fused(rc, C):
     return rc.cdt == torch.bfloat16 and C in K.SLAF_C
 
@@ -715,9 +757,9 @@ class UNetModel3D(nn.Module):
                  use_sparse_linear_attn=True, use_mid_attn=False, init_kernel_size=7, resnet_groups=8,
                  use_checkpoint=False, use_temp_attn=True, day_cond=False, year_cond=False, cond_map=True):
         super().__init__()
-        if not (use_temp_attn and cond_map) or day_cond or year_cond or use_mid_attn:
-            raise NotImplementedError("only the configuration model.UNet builds is supported "
-                                      "(temporal attention, cond map, no day/year cond, no mid attn)")
+        if not cond_map or day_cond or year_cond or use_mid_attn:
+            raise NotImplementedError("only the configurations model.UNet builds are supported "
+                                      "(cond map, no day/year cond, no mid attn)")
         if not 1 <= n_vars <= MAX_VARS:
             raise NotImplementedError(f"n_vars must be 1 … {MAX_VARS} target variables (the stem and head kernels' "
                                       f"limit), got {n_vars}")
@@ -728,13 +770,18 @@ class UNetModel3D(nn.Module):
         self.input_conv = nn.Conv3d(in_ch, model_dim, (1, init_kernel_size, init_kernel_size),
                                     padding=(0, pad, pad))
         rotary = RotaryEmbedding(min(32, attn_dim_head))
-        self.time_rel_pos_bias = RelativePositionBias(heads=attn_heads, max_distance=32)
+        if use_temp_attn:  # the reference builds the table twice then (video_net.py:603-632): same RNG draws
+            self.time_rel_pos_bias = RelativePositionBias(heads=attn_heads, max_distance=32)
         self.time_rel_pos_bias = RelativePositionBias(heads=attn_heads, max_distance=32)
 
         def tattn(dim):
             return EinopsToAndFrom(Attention(dim, heads=attn_heads, dim_head=attn_dim_head, rotary_emb=rotary))
 
-        self.input_temp_op = Residual(PreNorm(model_dim, tattn(model_dim)))
+        def top(dim, has_attn=False):
+            # use_temp_attn=False: a temporal conv in the input op and on every level but the three deepest
+            return tattn(dim) if use_temp_attn or has_attn else TemporalCNN(dim)
+
+        self.input_temp_op = Residual(PreNorm(model_dim, top(model_dim)))
         dims = [model_dim, *[int(model_dim * m) for m in dim_mults]]
         in_out = list(zip(dims[:-1], dims[1:]))
         time_dim = model_dim * 4
@@ -755,7 +802,7 @@ class UNetModel3D(nn.Module):
             self.downs.append(nn.ModuleList([
                 rb(din, dout), rb(dout, dout),
                 sla(dout) if use_sparse_linear_attn else nn.Identity(),
-                Residual(PreNorm(dout, tattn(dout))),
+                Residual(PreNorm(dout, top(dout, i >= nres - 3))),
                 Downsample(dout) if not last else nn.Identity(),
             ]))
         mid = dims[-1]
@@ -768,7 +815,7 @@ class UNetModel3D(nn.Module):
             self.ups.append(nn.ModuleList([
                 rb(dout * 2, din), rb(din, din),
                 sla(din) if use_sparse_linear_attn else nn.Identity(),
-                Residual(PreNorm(din, tattn(din))),
+                Residual(PreNorm(din, top(din, i < 3))),
                 Upsample(din) if not last else nn.Identity(),
             ]))
         self.out_conv = nn.Sequential(ResnetBlock(model_dim * 2, model_dim, groups=resnet_groups),
@@ -830,12 +877,12 @@ class UNetModel3D(nn.Module):
         rc = RunCtx(self, B, F, cdt, save)
         rpb = self.time_rel_pos_bias
         rc.bias = K.relpos_fwd(rpb.relative_attention_bias.weight, F, rpb.num_buckets, rpb.max_distance)
-        rc.rot = K.rope_table(self.input_temp_op.fn.fn.fn.rotary_emb.freqs, F)
+        rc.rot = K.rope_table(self.mid_temporal_attn.fn.fn.fn.rotary_emb.freqs, F)
         tape = SimpleNamespace(rc=rc, x_t=x_t, cond=cond, downs=[], ups=[])
 
         x = K.stem_fwd(x_t, cond, self.input_conv.weight, self.input_conv.bias, F, cdt)
         tape.stem_out = x
-        x, tape.in_attn = tattn_fwd(rc, self.input_temp_op, x)
+        x, tape.in_attn = temporal_fwd(rc, self.input_temp_op, x)
         r = x
         emb = K.sinusoidal(t, self.time_mlp[0].dim)
         h1 = K.linear_small(emb, self.time_mlp[1].weight, self.time_mlp[1].bias, False)
@@ -848,7 +895,7 @@ class UNetModel3D(nn.Module):
             x, s.b2 = resnet_fwd(rc, b2, x, None, temb)
             if not isinstance(sa, nn.Identity):
                 x, s.sa = sla_fwd(rc, sa, x)
-            x, s.ta = tattn_fwd(rc, ta, x)
+            x, s.ta = temporal_fwd(rc, ta, x)
             hs.append(x)
             s.down = None
             if not isinstance(down, nn.Identity):
@@ -864,7 +911,7 @@ class UNetModel3D(nn.Module):
             x, s.b2 = resnet_fwd(rc, b2, x, None, temb)
             if not isinstance(sa, nn.Identity):
                 x, s.sa = sla_fwd(rc, sa, x)
-            x, s.ta = tattn_fwd(rc, ta, x)
+            x, s.ta = temporal_fwd(rc, ta, x)
             s.up = None
             if not isinstance(up, nn.Identity):
                 x, s.up = conv_forward(rc, ConvSpec(up), x)
@@ -924,7 +971,7 @@ class UNetModel3D(nn.Module):
             s = tape.ups[j]
             if s.up is not None:
                 dx = conv_backward(rc, ConvSpec(up), s.up, dx)
-            dx = tattn_bwd(rc, ta, s.ta, dx)
+            dx = temporal_bwd(rc, ta, s.ta, dx)
             if not isinstance(sa, nn.Identity):
                 dx = sla_bwd(rc, sa, s.sa, dx)
             dx = resnet_bwd(rc, b2, s.b2, dx)
@@ -942,14 +989,14 @@ class UNetModel3D(nn.Module):
                 dx = conv_backward(rc, ConvSpec(down), s.down, dx, True, dres1=dskips[i])
             else:
                 dx = K.add(dx, dskips[i])
-            dx = tattn_bwd(rc, ta, s.ta, dx)
+            dx = temporal_bwd(rc, ta, s.ta, dx)
             if not isinstance(sa, nn.Identity):
                 dx = sla_bwd(rc, sa, s.sa, dx)
             dx = resnet_bwd(rc, b2, s.b2, dx)
             dx = resnet_bwd(rc, b1, s.b1, dx)
             done(self.downs[i])
         dx = K.add(dx, dr)
-        dx = tattn_bwd(rc, self.input_temp_op, tape.in_attn, dx)
+        dx = temporal_bwd(rc, self.input_temp_op, tape.in_attn, dx)
         wi, bi = gbuf(self.input_conv.weight), gbuf(self.input_conv.bias)
         with rc.side(tape.x_t, tape.cond, dx):
             if wi is not None:

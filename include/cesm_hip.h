@@ -38,8 +38,9 @@ extern "C" {
  *     job table gained per-job block starts and its fourth argument is the grid size;
  *     cesm_qkv_bwd / cesm_qkv_bwd_streams added;
  *   7: cesm_conv_wgrad_sq_bn removed; cesm_conv_wgrad_nsplit, cesm_conv_wgrad_bias_rides and cesm_conv_pack_blocks
- *     added (host-only queries: the weight-gradient split count and the pack tiling now come from the library). */
-#define CESM_ABI_VERSION 7
+ *     added (host-only queries: the weight-gradient split count and the pack tiling now come from the library);
+ *   8: cesm_tconv_fwd / cesm_tconv_bwd and their host-only queries added (temporal-convolution blocks). */
+#define CESM_ABI_VERSION 8
 int cesm_abi_version(void);
 /* Measurement aid, not a training op: nblk blocks that each occupy one whole CU (full LDS) for `usec` microseconds on
  * `stream` -- the one-GPU stand-in for the RCCL kernels of an overlapped gradient all-reduce (tools/overlap_sim.py,
@@ -195,6 +196,29 @@ int cesm_ln_fwd(int dtype, const void* x, const float* gamma, void* out, float* 
 int cesm_ln_bwd(int dtype, const void* dy, const void* x, const float* mr, const float* gamma, const void* dres,
                 void* dx, float* dgamma, float* part, int nblk, int64_t V, int C, int accumulate, int perm_f, int perm_hw,
                 hipStream_t stream);
+
+/* ---- temporal-convolution blocks (csrc/tconv.h, included from norm.hip) ---------------------
+ * Residual(PreNorm(TemporalCNN)) of UNet(use_temp_attn=False): n = LN_C(x) * gamma (biased variance),
+ *   y[b,f,p,:] = x[b,f,p,:] + bias + sum_k W[:,:,k] n[b,f+k-1,p,:]      (n = 0 for frames outside 0 .. F-1)
+ * x, y, dy, dx [B*F][HW][C] of `dtype`, C in {64, 128, 256} (cesm_tconv_supported; else CESM_EUNSUPPORTED), any
+ * F >= 1 and HW >= 1.  wp / wpt: the Conv1d weight [C][C][3] packed by cesm_conv_pack(dtype, w, out, C, C, 1, 3, s, s)
+ * with s = 0 (wp, forward) and s = 1 (wpt, swapped and flipped: backward).  mr [B*F*HW][2] (mean, rstd): written by
+ * the forward when non-null, read by the backward.  ws / ws_n / ws_dn: [B*F*HW][C] of dtype, fp32 path only (bf16:
+ * ignored, may be null).
+ * Backward: dx = LN backward of dn = sum_k W[:,:,k]^T dy[b,f-k+1,p,:], + dy; dgamma [C], dw [C][C][3] (the Conv1d
+ * weight's layout), db [C] fp32, each (+)= and each nullable (then not computed, nothing written for it).  part /
+ * slab: fp32 workspaces of cesm_tconv_part_floats / cesm_tconv_slab_floats elements (0 = unsupported shape); part is
+ * needed when dgamma or db is asked for (fp32 path: always), slab when dw is.  Every reduction is over fixed-order
+ * partial sums (no atomics): results are bit-repeatable.  bf16 runs MFMA kernels (one read of x and one write of y in
+ * the forward); fp32 is the parity path (LayerNorm kernels + plain FMA). */
+int cesm_tconv_supported(int C);
+int64_t cesm_tconv_part_floats(int dtype, int B, int F, int HW, int C);
+int64_t cesm_tconv_slab_floats(int dtype, int B, int F, int HW, int C);
+int cesm_tconv_fwd(int dtype, const void* x, const float* gamma, const void* wp, const float* bias, void* y, float* mr,
+                   void* ws, int B, int F, int HW, int C, float eps, hipStream_t stream);
+int cesm_tconv_bwd(int dtype, const void* x, const void* dy, const float* mr, const float* gamma, const void* wpt, void* dx,
+                   float* dgamma, float* dw, float* db, float* part, float* slab, void* ws_n, void* ws_dn, int B, int F,
+                   int HW, int C, float eps, int accumulate, hipStream_t stream);
 
 /* ---- attention (csrc/attn.hip) -----------------------------------------------------------
  * RoPE angle table (rotary_embedding.py:143-144, :275-278): rot[f][i] = (cos, sin)(f*freqs[i]). */
