@@ -45,9 +45,17 @@ static int gn_nchunk(int64_t rows_b, int C, int B) {
 }
 
 // part[b][chunk][g] = (sum, sumsq) as double
+// One pass: the variance is E[y^2] - mean^2, which cancels as (mean / std)^2 grows.  bf16 values carry 8 significant
+// bits, so their squares and short sums are nearly exact in fp32 per-thread sums (measured at |mean| = 32 std: 1.7e-6).
+// fp32 (parity mode) values are not: with fp32 sums rstd was off by 3e-5 to 5e-5 there, over the 1e-5 parity bound
+// (tests/test_gpu_norm.py::test_gn_offset).  So the fp32 instantiation also adds every thread's values in double, and a
+// block writes the double sums of a group whose rows in this chunk lie more than GN_OFFSET_STD standard deviations off
+// zero, the fp32 ones (the sums of every centred group, bit for bit what they always were) otherwise.
+constexpr double GN_OFFSET_STD = 4.0;  // fp32 sums at 4 std: 0.16 of the parity bound, growing with the square
 template <typename T>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ y, double* __restrict__ part,
                                                        int64_t rows_b, int C, int G, int nchunk) {
+  constexpr bool DBL = std::is_same<T, float>::value;
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int cv = C / 8, rl = 256 / cv;
   const int tid = threadIdx.x;
@@ -57,24 +65,39 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ y, 
   const int64_t r0 = chunk * rpc, r1 = min(rows_b, r0 + rpc);
   const T* base = y + (int64_t)b * rows_b * C;
   float s = 0.f, ss = 0.f;
+  double sd = 0.0, ssd = 0.0;
   if (rr < rl) {
 #pragma unroll 4
     for (int64_t r = r0 + rr; r < r1; r += rl) {
       float v[8];
       gl8(base + r * C + c8 * 8, v);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) { s += v[i]; ss = fmaf(v[i], v[i], ss); }
+      for (int i = 0; i < 8; ++i) {
+        s += v[i];
+        ss = fmaf(v[i], v[i], ss);
+        if constexpr (DBL) { sd += v[i]; ssd = fma((double)v[i], (double)v[i], ssd); }
+      }
     }
   }
   __shared__ double red[256][2];
+  __shared__ double redd[DBL ? 256 : 1][2];
   red[tid][0] = s;
   red[tid][1] = ss;
+  if constexpr (DBL) { redd[tid][0] = sd; redd[tid][1] = ssd; }
   __syncthreads();
   if (tid < G) {
     double a = 0.0, q = 0.0;
     const int g8 = gsz / 8;  // 8-channel groups per GroupNorm group (gsz % 8 == 0 checked on host)
     for (int k = 0; k < rl; ++k)
       for (int c = tid * g8; c < (tid + 1) * g8; ++c) { a += red[k * cv + c][0]; q += red[k * cv + c][1]; }
+    if constexpr (DBL) {
+      double ad = 0.0, qd = 0.0;
+      for (int k = 0; k < rl; ++k)
+        for (int c = tid * g8; c < (tid + 1) * g8; ++c) { ad += redd[k * cv + c][0]; qd += redd[k * cv + c][1]; }
+      const double n = (double)(r1 > r0 ? r1 - r0 : 0) * gsz;  // this chunk's elements of the group
+      // ad^2 / n = n mean^2, qd - ad^2 / n = n var
+      if (n > 0 && ad * ad > GN_OFFSET_STD * GN_OFFSET_STD * (n * qd - ad * ad)) { a = ad; q = qd; }
+    }
     double* o = part + (((int64_t)b * nchunk + chunk) * G + tid) * 2;
     o[0] = a;
     o[1] = q;
@@ -551,6 +574,17 @@ static int gn_apply_chunks(int64_t rows_b, int C) {
 
 extern "C" {
 
+// Host-only plan queries: the chunk counts the launchers below use (the same functions), so a test can name the
+// regime a shape lands in (capped, ragged or empty last chunk) without restating the formulas.  -1: no plan.
+int cesm_gn_nchunk(int64_t rows_b, int C, int B) {
+  if (rows_b < 1 || B < 1 || C < 8 || C % 8 || C / 8 > 256) return -1;
+  return gn_nchunk(rows_b, C, B);
+}
+int cesm_gn_apply_nchunk(int64_t rows, int C) {
+  if (rows < 1 || C < 8 || C % 8 || C / 8 > 256) return -1;
+  return gn_apply_chunks(rows, C);
+}
+
 // y: [B][rows_b][C] (rows_b = F*H*W); writes stats[B][G][2] = (mean, rstd); ws >= max(B*256, 1024)*G*2 doubles
 int cesm_gn_stats(int dtype, const void* y, float* stats, double* ws, int B, int64_t rows_b, int C, int G, float eps,
                   hipStream_t stream) {
@@ -588,7 +622,8 @@ int cesm_gn_stats_part(float* part, float* stats, int B, int64_t nslot, int C, i
 static int gn_apply_launch(int dtype, const void* y, const float* stats, const float* gamma, const float* beta,
                            const float* ss, const void* res, void* out, int B, int64_t rows_b, int C, int G,
                            const GnWin* win, hipStream_t stream) {
-  if (C % 8 || C / 8 > 256 || C % G) return CESM_EINVAL;
+  // (C / G) % 8: a thread's 8 channels take one group's statistics (gn_coef8)
+  if (C % 8 || C / 8 > 256 || C % G || (C / G) % 8) return CESM_EINVAL;
   const GnAffine aff{stats, gamma, beta, ss, G};
   const int nch = gn_apply_chunks(win ? win->n : rows_b, C);
   int rc = dispatch_dt(dtype, [&](auto* tp) {
@@ -629,11 +664,15 @@ int cesm_gn_apply_rows(int dtype, const void* y, const float* stats, const float
 // Backward of out = silu(GN(y)*(1+scale)+shift) (+res).  Writes dy, dss [B][2C] (if non-null),
 // dgamma/dbeta and the producing conv's bias gradient dbias = sum dy (each nullable; accumulate flag).
 // ws: float workspace >= B*1024*C*3 + B*C*3 + B*C*5 floats.
+// Widths: C / 8 a power of two and <= 128, C / G one of 8, 16, 32, 64, G <= 64; anything else is CESM_EINVAL.
 static int gn_bwd_launch(int dtype, const void* dout, const void* y, const float* stats, const float* gamma,
                          const float* beta, const float* ss, void* dy, float* dss, float* dgamma, float* dbeta,
                          float* dbias, float* ws, int B, int64_t rows_b, int C, int G, int accumulate,
                          const GnWin* win, hipStream_t stream) {
-  if (C % 8 || C / 8 > 128 || C % G || C / G > 64 || 64 % (C / G) || G > 64) return CESM_EINVAL;
+  if (C % 8 || C / 8 > 128 || C % G || (C / G) % 8 || C / G > 64 || 64 % (C / G) || G > 64) return CESM_EINVAL;
+  // the reduction adds the lanes that share a channel vector with xor shuffles at offsets cv, 2 cv, ...: a sum only
+  // for a power-of-two cv = C / 8 (C = 192 would pass the guards above and add the wrong lanes)
+  if ((C / 8) & (C / 8 - 1)) return CESM_EINVAL;
   const double count = (double)rows_b * (C / G);
   const GnAffine aff{stats, gamma, beta, ss, G};
   const int nch = gn_apply_chunks(rows_b, C);

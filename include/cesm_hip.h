@@ -166,9 +166,22 @@ int cesm_gn_stats_part(float* part, float* stats, int B, int64_t nslot, int C, i
 int cesm_gn_apply(int dtype, const void* y, const float* stats, const float* gamma, const float* beta,
                   const float* ss, const void* res, void* out, float* ws, int B, int64_t rows_b, int C, int G,
                   hipStream_t stream);
+/* Host-only queries of the launch plan (no GPU work): the row chunks per sample of the reduction kernels
+ * (cesm_gn_stats, and cesm_gn_bwd's reduction; chunk k covers rows [k r, min(rows_b, (k + 1) r)) with
+ * r = ceil(rows_b / chunks), so a trailing chunk can be ragged or empty) and of the streaming kernels (cesm_gn_apply,
+ * cesm_gn_bwd's apply pass; `rows` = rows_b, or the window's row_n for cesm_gn_apply_rows).  These are what the
+ * launchers themselves call.  -1 for a size < 1 or a C the forward refuses.  Added entry points (no existing argument
+ * list changed): the ABI version stays, as for cesm_stem_dgrad. */
+int cesm_gn_nchunk(int64_t rows_b, int C, int B);
+int cesm_gn_apply_nchunk(int64_t rows, int C);
 /* backward; also writes the producing conv's bias gradient dbias (+)= sum dy (nullable) without another
  * pass over dy.  ws >= max(B*1024, 1024)*C*3 + B*C*3 + B*C*5 floats (max(B*256, 1024) suffices in the default
- * build; builds with -DGN_BIGB_CAP=512/1024 or -DGN_PER_SAMPLE=1 use up to 1024 chunk partials per sample). */
+ * build; builds with -DGN_BIGB_CAP=512/1024 or -DGN_PER_SAMPLE=1 use up to 1024 chunk partials per sample).
+ * Width rule: C / 8 must be a power of two and <= 128 (the reduction adds the lanes that share a channel vector with
+ * xor shuffles), C / G one of 8, 16, 32, 64 and G <= 64; any other width returns CESM_EINVAL.  The forward
+ * (cesm_gn_stats, cesm_gn_apply) is wider: any C % 8 == 0 up to 2048 with (C / G) % 8 == 0, C = 192 included.
+ * dss, dgamma, dbeta and dbias are each nullable (then not written); accumulate = 0 overwrites the three parameter
+ * gradients, 1 adds to them; dss is always overwritten.  The workspace need not be initialised. */
 int cesm_gn_bwd(int dtype, const void* dout, const void* y, const float* stats, const float* gamma,
                 const float* beta, const float* ss, void* dy, float* dss, float* dgamma, float* dbeta, float* dbias,
                 float* ws, int B, int64_t rows_b, int C, int G, int accumulate, hipStream_t stream);
