@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 
 from .model import UNet, Diffusion
+from .train import guidance_p_uncond
 
 
 def _plain_norm(norm):
@@ -75,7 +76,8 @@ def build_from_config(cfg, device):
                 groups=unet_cfg.get("groups", 8), dropout=unet_cfg.get("dropout", 0.0),
                 use_temp_attn=unet_cfg.get("use_temp_attn", True)).to(device)
     diffusion = Diffusion(unet, img_channels=1, timesteps=train_cfg.get("timesteps", 1000),
-                          beta_schedule=train_cfg.get("beta_schedule", "linear")).to(device)
+                          beta_schedule=train_cfg.get("beta_schedule", "linear"),
+                          p_uncond=guidance_p_uncond(train_cfg)).to(device)
     return unet, diffusion
 
 

@@ -114,23 +114,43 @@ __global__ void q_sample_kernel(const float* __restrict__ x0, const float* __res
   }
 }
 
+// The guidance combine of the *_cfg kernels (classifier-free guidance, Ho & Salimans 2022): eps_g = eps_u + s (eps_c -
+// eps_u), one subtraction and one FMA, each named so that no contraction choice can move it.  s (eu - eu) is an exact
+// zero for finite eu, so equal halves give eps_c back bit for bit.
+__device__ __forceinline__ float cfg_combine(float scale, float ec, float eu) {
+  return __fmaf_rn(scale, __fsub_rn(ec, eu), eu);
+}
+
+// The three update kernels take the guidance scale as a trailing parameter pack S: empty for the unguided kernels,
+// whose argument lists (and code) are those from before guidance existed, {float} for the *_cfg entries (GUIDED).
+__device__ __forceinline__ float cfg_scale() { return 1.f; }
+__device__ __forceinline__ float cfg_scale(float s) { return s; }
+
 // DDPM ancestral step (model.py:168-183), fused:
 //   x_{t-1} = r_t (x_t - (b_t / s1_t) eps) + sqrt(pv_t) z
 // with the reference's operation order and no contraction (agrees with the eager torch expression to
 // fp32 rounding).  pv_0 = 0 (alphas_cumprod_prev[0] = 1), so the t = 0 step adds no noise either way;
 // z == nullptr skips the noise term (the reference's `(t == 0).all()` branch).  out may alias x.
+// GUIDED: B counts samples, x / eps / out have 2 B rows: eps rows [0, B) are eps_c and rows [B, 2B) eps_u, x is read
+// from rows [0, B) only, and x_prev goes to row b and to row b + B (the next evaluation's two halves); z has B rows.
+template <typename... S>
 __global__ void ddpm_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
                                  const float* __restrict__ z, const int64_t* __restrict__ t,
                                  const float* __restrict__ sra, const float* __restrict__ betas,
                                  const float* __restrict__ s1a, const float* __restrict__ pv, float* out, int B,
-                                 int64_t HW) {
+                                 int64_t HW, S... sc) {
+  constexpr bool GUIDED = sizeof...(S) != 0;
   const int64_t n = (int64_t)B * HW;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
     const int64_t ti = t[e / HW];
     const float c = __fdiv_rn(betas[ti], s1a[ti]);
-    float m = __fmul_rn(sra[ti], __fsub_rn(x[e], __fmul_rn(c, eps[e])));
+    const float xv = x[e];
+    float ev = eps[e];
+    if constexpr (GUIDED) ev = cfg_combine(cfg_scale(sc...), ev, eps[e + n]);
+    float m = __fmul_rn(sra[ti], __fsub_rn(xv, __fmul_rn(c, ev)));
     if (z) m = __fadd_rn(m, __fmul_rn(__fsqrt_rn(pv[ti]), z[e]));
     out[e] = m;
+    if constexpr (GUIDED) out[e + n] = m;
   }
 }
 
@@ -145,12 +165,15 @@ __global__ void ddpm_step_kernel(const float* __restrict__ x, const float* __res
 // every thread two table reads; VEC: HW % 4 == 0 and every pointer 16-byte aligned -> 16-byte accesses (no tail is
 // left then), else one element per access.  z == nullptr: no noise term, z is not read.  out may alias x (each thread
 // reads its elements before it writes them), so neither carries __restrict__.
-template <bool VEC>
+// GUIDED (cesm_ddim_step_cfg): gridDim.y = B samples, x / eps / out have 2 B rows as in ddpm_step_kernel; sample b
+// reads x row b, eps rows b and b + B, and writes rows b and b + B of out; t, t_prev and z have B rows.
+template <bool VEC, typename... S>
 __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const float* __restrict__ eps,
                                                         const float* __restrict__ z, const int64_t* __restrict__ t,
                                                         const int64_t* __restrict__ tprev,
                                                         const float* __restrict__ acp, float eta, float* out,
-                                                        int64_t HW) {
+                                                        int64_t HW, S... sc) {
+  constexpr bool GUIDED = sizeof...(S) != 0;
   const int b = blockIdx.y;
   const int64_t tp = tprev[b];
   const double ac = (double)acp[t[b]];
@@ -160,6 +183,7 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const fl
   const float cb = (float)(sqrt(fmax(1.0 - ap - sg * sg, 0.0)) - sqrt(ap * (1.0 - ac) / ac));
   const float cs = (float)sg;
   const int64_t base = (int64_t)b * HW;
+  const int64_t half = (int64_t)gridDim.y * HW;  // GUIDED: the distance from a row to its twin in the other half
   x += base, eps += base, out += base;
   if (z) z += base;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -169,6 +193,12 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const fl
       float xv[4], ev[4], m[4];
       load4(x + e * 4, xv);
       load4(eps + e * 4, ev);
+      if constexpr (GUIDED) {
+        float uv[4];
+        load4(eps + half + e * 4, uv);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ev[i] = cfg_combine(cfg_scale(sc...), ev[i], uv[i]);
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) m[i] = ca * xv[i] + cb * ev[i];
       if (z) {
@@ -178,12 +208,17 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const fl
         for (int i = 0; i < 4; ++i) m[i] += cs * zv[i];
       }
       store4(out + e * 4, m);
+      if constexpr (GUIDED) store4(out + half + e * 4, m);
     }
   } else {
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < HW; e += stride) {
-      float m = ca * x[e] + cb * eps[e];
+      const float xv = x[e];
+      float ev = eps[e];
+      if constexpr (GUIDED) ev = cfg_combine(cfg_scale(sc...), ev, eps[half + e]);
+      float m = ca * xv + cb * ev;
       if (z) m += cs * z[e];
       out[e] = m;
+      if constexpr (GUIDED) out[half + e] = m;
     }
   }
 }
@@ -201,13 +236,16 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const fl
 // elements before it writes them), so none of the four carries __restrict__.
 __device__ __forceinline__ int64_t clamp_i64(int64_t v, int64_t hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
-template <bool VEC>
+// GUIDED (cesm_dpmpp_step_cfg): gridDim.y = B samples, x / eps / out have 2 B rows as in ddpm_step_kernel; x0_last,
+// x0_out, t, t_prev and t_last have B rows.
+template <bool VEC, typename... S>
 __global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const float* __restrict__ eps,
                                                          const float* x0_last, const int64_t* __restrict__ t,
                                                          const int64_t* __restrict__ tprev,
                                                          const int64_t* __restrict__ tlast,
                                                          const float* __restrict__ acp, float* out, float* x0_out,
-                                                         int64_t HW, int T) {
+                                                         int64_t HW, int T, S... sc) {
+  constexpr bool GUIDED = sizeof...(S) != 0;
   __shared__ float coef[5];
   const int b = blockIdx.y;
   const int64_t tp = tprev[b], tl = tlast[b];
@@ -238,6 +276,7 @@ __global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const f
   __syncthreads();
   const float ca = coef[0], cb = coef[1], cc = coef[2], c1 = coef[3], c2 = coef[4];
   const int64_t base = (int64_t)b * HW;
+  const int64_t half = (int64_t)gridDim.y * HW;  // GUIDED: the distance from a row to its twin in the other half
   x += base, eps += base, out += base, x0_out += base;
   if (hist) x0_last += base;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -247,6 +286,12 @@ __global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const f
       float xv[4], ev[4], m[4], p[4];
       load4(x + e * 4, xv);
       load4(eps + e * 4, ev);
+      if constexpr (GUIDED) {
+        float uv[4];
+        load4(eps + half + e * 4, uv);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ev[i] = cfg_combine(cfg_scale(sc...), ev[i], uv[i]);
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) m[i] = ca * xv[i] + cb * ev[i];
       if (hist) {
@@ -258,16 +303,44 @@ __global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const f
 #pragma unroll
       for (int i = 0; i < 4; ++i) p[i] = c1 * xv[i] + c2 * ev[i];
       store4(out + e * 4, m);
+      if constexpr (GUIDED) store4(out + half + e * 4, m);
       store4(x0_out + e * 4, p);
     }
   } else {
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < HW; e += stride) {
-      const float xv = x[e], ev = eps[e];
+      const float xv = x[e];
+      float ev = eps[e];
+      if constexpr (GUIDED) ev = cfg_combine(cfg_scale(sc...), ev, eps[half + e]);
       float m = ca * xv + cb * ev;
       if (hist) m += cc * x0_last[e];
       out[e] = m;
+      if constexpr (GUIDED) out[half + e] = m;
       x0_out[e] = c1 * xv + c2 * ev;
     }
+  }
+}
+
+// Condition dropout of classifier-free-guidance training (cesm_cond_mask): out[b] = keep[b] ? cond[b] : 0 over the n
+// elements of sample b = blockIdx.y.  A select, not a multiply: a dropped sample's cond is not read.  out may alias
+// cond (each thread reads its elements before it writes them), so neither carries __restrict__.  VEC as in
+// ddim_step_kernel.
+template <bool VEC>
+__global__ __launch_bounds__(256) void cond_mask_kernel(const float* cond, const unsigned char* __restrict__ keep,
+                                                        float* out, int64_t n) {
+  const int b = blockIdx.y;
+  const bool k = keep[b] != 0;
+  const int64_t base = (int64_t)b * n;
+  cond += base, out += base;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (VEC) {
+    const int64_t nv = n >> 2;
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < nv; e += stride) {
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+      if (k) load4(cond + e * 4, v);
+      store4(out + e * 4, v);
+    }
+  } else {
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += stride) out[e] = k ? cond[e] : 0.f;
   }
 }
 
@@ -802,7 +875,7 @@ int cesm_ddpm_step(const float* x, const float* eps, const float* z, const int64
                    int B, int64_t HW, hipStream_t stream) {
   if (B < 1 || HW < 1) return CESM_EINVAL;
   const unsigned grid = (unsigned)std::min<int64_t>(cdiv((int64_t)B * HW, 256), 4096);
-  ddpm_step_kernel<<<grid, 256, 0, stream>>>(x, eps, z, t, sqrt_recip_alphas, betas, sqrt_one_minus_ac,
+  ddpm_step_kernel<><<<grid, 256, 0, stream>>>(x, eps, z, t, sqrt_recip_alphas, betas, sqrt_one_minus_ac,
                                              posterior_variance, out, B, HW);
   return cesm_launch_status();
 }
@@ -838,6 +911,67 @@ int cesm_dpmpp_step(const float* x, const float* eps, const float* x0_last, cons
   else
     dpmpp_step_kernel<false><<<grid, 256, 0, stream>>>(x, eps, x0_last, t, t_prev, t_last, alphas_cumprod, out, x0_out,
                                                        HW, T);
+  return cesm_launch_status();
+}
+
+// The three guided updates: the grids of their unguided entries over B samples; x, eps, out hold 2 B rows.
+int cesm_ddpm_step_cfg(const float* x, const float* eps, const float* z, const int64_t* t,
+                       const float* sqrt_recip_alphas, const float* betas, const float* sqrt_one_minus_ac,
+                       const float* posterior_variance, float* out, int B, int64_t HW, float scale,
+                       hipStream_t stream) {
+  if (!x || !eps || !t || !sqrt_recip_alphas || !betas || !sqrt_one_minus_ac || !posterior_variance || !out)
+    return CESM_EINVAL;
+  if (B < 1 || HW < 1 || !(scale >= 0.f && std::isfinite(scale))) return CESM_EINVAL;
+  const unsigned grid = (unsigned)std::min<int64_t>(cdiv((int64_t)B * HW, 256), 4096);
+  ddpm_step_kernel<float><<<grid, 256, 0, stream>>>(x, eps, z, t, sqrt_recip_alphas, betas, sqrt_one_minus_ac,
+                                                 posterior_variance, out, B, HW, scale);
+  return cesm_launch_status();
+}
+
+int cesm_ddim_step_cfg(const float* x, const float* eps, const float* z, const int64_t* t, const int64_t* t_prev,
+                       const float* alphas_cumprod, float eta, float* out, int B, int64_t HW, int T, float scale,
+                       hipStream_t stream) {
+  if (!x || !eps || !t || !t_prev || !alphas_cumprod || !out) return CESM_EINVAL;
+  if (B < 1 || B > 65535 || HW < 1 || T < 1 || !(eta >= 0.f) || !(scale >= 0.f && std::isfinite(scale)))
+    return CESM_EINVAL;
+  if (eta == 0.f) z = nullptr;
+  const bool vec = HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)eps | (uintptr_t)z | (uintptr_t)out) & 15) == 0;
+  const int64_t per = std::max<int64_t>(1, 4096 / B);
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv(vec ? HW / 4 : HW, 256), per), (unsigned)B);
+  if (vec)
+    ddim_step_kernel<true, float><<<grid, 256, 0, stream>>>(x, eps, z, t, t_prev, alphas_cumprod, eta, out, HW, scale);
+  else
+    ddim_step_kernel<false, float><<<grid, 256, 0, stream>>>(x, eps, z, t, t_prev, alphas_cumprod, eta, out, HW, scale);
+  return cesm_launch_status();
+}
+
+int cesm_dpmpp_step_cfg(const float* x, const float* eps, const float* x0_last, const int64_t* t,
+                        const int64_t* t_prev, const int64_t* t_last, const float* alphas_cumprod, float* out,
+                        float* x0_out, int B, int64_t HW, int T, float scale, hipStream_t stream) {
+  if (!x || !eps || !t || !t_prev || !t_last || !alphas_cumprod || !out || !x0_out) return CESM_EINVAL;
+  if (B < 1 || B > 65535 || HW < 1 || T < 1 || !(scale >= 0.f && std::isfinite(scale))) return CESM_EINVAL;
+  const bool vec = HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)eps | (uintptr_t)x0_last | (uintptr_t)out |
+                                    (uintptr_t)x0_out) & 15) == 0;
+  const int64_t per = std::max<int64_t>(1, 4096 / B);
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv(vec ? HW / 4 : HW, 256), per), (unsigned)B);
+  if (vec)
+    dpmpp_step_kernel<true, float><<<grid, 256, 0, stream>>>(x, eps, x0_last, t, t_prev, t_last, alphas_cumprod, out,
+                                                          x0_out, HW, T, scale);
+  else
+    dpmpp_step_kernel<false, float><<<grid, 256, 0, stream>>>(x, eps, x0_last, t, t_prev, t_last, alphas_cumprod, out,
+                                                           x0_out, HW, T, scale);
+  return cesm_launch_status();
+}
+
+int cesm_cond_mask(const float* cond, const unsigned char* keep, float* out, int B, int64_t n, hipStream_t stream) {
+  if (!cond || !keep || !out || B < 1 || B > 65535 || n < 1) return CESM_EINVAL;
+  const bool vec = n % 4 == 0 && (((uintptr_t)cond | (uintptr_t)out) & 15) == 0;
+  const int64_t per = std::max<int64_t>(1, 4096 / B);
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv(vec ? n / 4 : n, 256), per), (unsigned)B);
+  if (vec)
+    cond_mask_kernel<true><<<grid, 256, 0, stream>>>(cond, keep, out, n);
+  else
+    cond_mask_kernel<false><<<grid, 256, 0, stream>>>(cond, keep, out, n);
   return cesm_launch_status();
 }
 

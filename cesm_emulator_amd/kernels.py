@@ -7,6 +7,8 @@ instead of faulting on the GPU.
 """
 from __future__ import annotations
 
+import math
+import numbers
 import os
 
 import torch
@@ -457,6 +459,8 @@ def rows_scatter(src_c, dst, B, row_lo, row_n):
 def ln_fwd(x, gamma, save=True, eps=1e-5, perm=None):
     """perm = (F, HW): write the output rows of voxel (b, f, p) at (b, p, f) -- pixel-major, a pixel's frames
     adjacent (mr stays in x's order)"""
+    if not (x.is_cuda and gamma.is_cuda):  # checked here, not left to the stream query: host pointers must not launch
+        raise RuntimeError("cesm_emulator_amd kernels need device tensors (no CPU fallback)")
     C = x.shape[-1]
     V = x.numel() // C
     out = empty(x.shape, x.dtype, x.device)
@@ -951,6 +955,104 @@ def dpmpp_step(x, eps, x0_last, t, t_prev, t_last, alphas_cumprod, out=None, x0_
     call("cesm_dpmpp_step", P(x), P(eps), P(x0_last), P(t), P(t_prev), P(t_last), P(alphas_cumprod), P(out), P(x0_out),
          B, x.numel() // B, alphas_cumprod.numel(), S())
     return out, x0_out
+
+
+def guidance_scale_arg(scale, name="scale"):
+    """a classifier-free-guidance scale as a float: a finite number >= 0 (no bool), else ValueError"""
+    if isinstance(scale, bool) or not isinstance(scale, numbers.Real):
+        raise ValueError(f"{name} must be a finite number >= 0, got {scale!r}")
+    s = float(scale)
+    if not (math.isfinite(s) and s >= 0.0):
+        raise ValueError(f"{name} must be a finite number >= 0, got {scale!r}")
+    return s
+
+
+def _cfg_rows(x, eps, out):
+    """the guided updates' x / eps / out: [2 B, ...] fp32 (eps_c rows, then eps_u rows); returns (B, HW, out)"""
+    _chk(x, dtype=torch.float32)
+    if x.ndim < 1 or x.shape[0] < 2 or x.shape[0] % 2:
+        raise RuntimeError(f"guided update: x needs 2 B rows (conditional half, unconditional half), got "
+                           f"{tuple(x.shape)}")
+    _chk(eps, x.shape, torch.float32)
+    if out is None:
+        out = empty(x.shape, torch.float32, x.device)
+    else:
+        _chk(out, x.shape, torch.float32)
+    B = x.shape[0] // 2
+    return B, x.numel() // (2 * B), out
+
+
+def ddpm_step_cfg(x, eps, z, t, sra, betas, s1a, pv, scale, out=None):
+    """ddpm_step with classifier-free guidance fused in (cesm_ddpm_step_cfg): x, eps, out [2 B, ...] -- eps rows
+    [0, B) are eps_c, rows [B, 2B) eps_u; x is read from rows [0, B) and x_prev written to both halves; z, t: B rows.
+    scale: a finite number >= 0.  out may be x."""
+    scale = guidance_scale_arg(scale)
+    B, HW, out = _cfg_rows(x, eps, out)
+    if z is not None:
+        _chk(z, (B, *x.shape[1:]), torch.float32)
+    _chk(t, (B,), torch.int64)
+    call("cesm_ddpm_step_cfg", P(x), P(eps), P(z), P(t), P(sra), P(betas), P(s1a), P(pv), P(out), B, HW, scale, S())
+    return out
+
+
+def ddim_step_cfg(x, eps, z, t, t_prev, alphas_cumprod, eta, scale, out=None):
+    """ddim_step with classifier-free guidance fused in (cesm_ddim_step_cfg): x, eps, out [2 B, ...] as in
+    ddpm_step_cfg; z, t, t_prev: B rows.  scale: a finite number >= 0.  out may be x."""
+    scale = guidance_scale_arg(scale)
+    B, HW, out = _cfg_rows(x, eps, out)
+    if z is not None:
+        _chk(z, (B, *x.shape[1:]), torch.float32)
+    _chk(t, (B,), torch.int64)
+    _chk(t_prev, (B,), torch.int64)
+    _chk(alphas_cumprod, dtype=torch.float32)
+    if alphas_cumprod.ndim != 1:
+        raise RuntimeError("alphas_cumprod must be 1-D")
+    eta = float(eta)
+    if not eta >= 0.0:
+        raise ValueError(f"eta must be >= 0, got {eta}")
+    call("cesm_ddim_step_cfg", P(x), P(eps), P(z), P(t), P(t_prev), P(alphas_cumprod), eta, P(out), B, HW,
+         alphas_cumprod.numel(), scale, S())
+    return out
+
+
+def dpmpp_step_cfg(x, eps, x0_last, t, t_prev, t_last, alphas_cumprod, scale, out=None, x0_out=None):
+    """dpmpp_step with classifier-free guidance fused in (cesm_dpmpp_step_cfg): returns (x_prev [2 B, ...], x0
+    [B, ...]).  x, eps, out [2 B, ...] as in ddpm_step_cfg; x0_last, x0_out, t, t_prev, t_last: B rows.  scale: a
+    finite number >= 0.  out may be x, x0_out may be x0_last."""
+    scale = guidance_scale_arg(scale)
+    B, HW, out = _cfg_rows(x, eps, out)
+    rows = (B, *x.shape[1:])
+    if x0_last is not None:
+        _chk(x0_last, rows, torch.float32)
+    _chk(t, (B,), torch.int64)
+    _chk(t_prev, (B,), torch.int64)
+    _chk(t_last, (B,), torch.int64)
+    _chk(alphas_cumprod, dtype=torch.float32)
+    if alphas_cumprod.ndim != 1:
+        raise RuntimeError("alphas_cumprod must be 1-D")
+    if x0_out is None:
+        x0_out = empty(rows, torch.float32, x.device)
+    else:
+        _chk(x0_out, rows, torch.float32)
+    call("cesm_dpmpp_step_cfg", P(x), P(eps), P(x0_last), P(t), P(t_prev), P(t_last), P(alphas_cumprod), P(out),
+         P(x0_out), B, HW, alphas_cumprod.numel(), scale, S())
+    return out, x0_out
+
+
+def cond_mask(cond, keep, out=None):
+    """out[b] = cond[b] where keep[b], else 0 (cesm_cond_mask: a select, a dropped sample's cond is not read).  cond
+    [B, ...] fp32, keep [B] bool on the device; out may be cond."""
+    _chk(cond, dtype=torch.float32)
+    if cond.ndim < 2 or cond.numel() < 1:
+        raise RuntimeError(f"cond must be a non-empty [B, ...], got {tuple(cond.shape)}")
+    B = cond.shape[0]
+    _chk(keep, (B,), torch.bool)
+    if out is None:
+        out = empty(cond.shape, torch.float32, cond.device)
+    else:
+        _chk(out, cond.shape, torch.float32)
+    call("cesm_cond_mask", P(cond), P(keep), P(out), B, cond.numel() // B, S())
+    return out
 
 
 def mse(pred, tgt):

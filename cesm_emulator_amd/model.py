@@ -120,6 +120,30 @@ class _WLoss(torch.autograd.Function):
         return d, None, None, None, None, None
 
 
+class _CondMask(torch.autograd.Function):
+    """K.cond_mask: cond with the dropped samples (keep False) set to zero; the backward applies the same kernel to the
+    incoming gradient, so a dropped sample's d cond is exactly zero"""
+
+    @staticmethod
+    def forward(ctx, cond, keep):
+        ctx.save_for_backward(keep)
+        return K.cond_mask(cond, keep)
+
+    @staticmethod
+    def backward(ctx, g):
+        keep, = ctx.saved_tensors
+        return K.cond_mask(g.float().contiguous(), keep), None
+
+
+def check_guidance_scale(guidance_scale):
+    """a sampler's guidance_scale as None (unguided: None or exactly 1.0) or a float (a finite number >= 0, else
+    ValueError)"""
+    if guidance_scale is None:
+        return None
+    s = K.guidance_scale_arg(guidance_scale, "guidance_scale")
+    return None if s == 1.0 else s
+
+
 def latitude_weights(lat):
     """Row weights of a regular lat-lon grid from its latitudes in degrees: clamp_min(cos(lat), 0) / (mean + 1e-8),
     in float64 on the host, rounded to fp32 once (a CPU tensor [Hg])."""
@@ -162,10 +186,19 @@ class Diffusion(nn.Module):
       min_snr_gamma   None or gamma > 0: sample b weighs min(1, gamma (1 - ac_t) / ac_t) at its timestep t;
       lat   latitudes in degrees of the FULL grid's rows (length Hg), or None: then the tensor's own H rows span
             linspace(-90, 90, H), as the reference's _latitude_weights, and a crop offset makes no sense.
-    The weights are normalised over the full grid, so an equatorial crop weighs more than a polar one."""
+    The weights are normalised over the full grid, so an equatorial crop weighs more than a polar one.
+
+    Classifier-free guidance (Ho & Salimans 2022; off by default): the null condition is the all-zero cond (the data
+    path z-scores emissions, so zero is the climatological mean); there is no learned null token and no new parameter.
+      p_uncond   in [0, 1]: in training mode every sample's cond is dropped (zeroed) with this probability, so the one
+                 network learns eps(x, cond) and eps(x, 0).  A plain attribute: state_dict() keeps the 8 buffers.
+      guidance_scale (the samplers' argument)   None or 1.0: the conditional sampler, as without it; another finite
+                 s >= 0: eps = eps(x, 0) + s (eps(x, cond) - eps(x, 0)) from ONE network evaluation per step on 2 B
+                 rows and a fused update kernel; s = 0 is the unconditional sampler.  A model trained with
+                 p_uncond = 0 may be sampled with guidance too, but its unconditional branch was never trained."""
 
     def __init__(self, model, img_channels=1, timesteps=1000, beta_schedule="linear", lat_weight=0.0,
-                 min_snr_gamma=None, lat=None):
+                 min_snr_gamma=None, lat=None, p_uncond=0.0):
         super().__init__()
         self.model = model
         self.img_channels = img_channels
@@ -180,6 +213,9 @@ class Diffusion(nn.Module):
                 raise ValueError(f"min_snr_gamma must be None or a number > 0, got {min_snr_gamma!r}")
             min_snr_gamma = float(min_snr_gamma)
         self.min_snr_gamma = min_snr_gamma
+        if isinstance(p_uncond, bool) or not isinstance(p_uncond, numbers.Real) or not 0.0 <= p_uncond <= 1.0:
+            raise ValueError(f"p_uncond must be a probability in [0, 1], got {p_uncond!r}")
+        self.p_uncond = float(p_uncond)  # a plain attribute, not a buffer
         self._lat = None if lat is None else torch.as_tensor(lat, dtype=torch.float64, device="cpu").reshape(-1)
         if self._lat is not None and self._lat.numel() < 1:
             raise ValueError("lat must hold the latitude of every grid row")
@@ -216,23 +252,33 @@ class Diffusion(nn.Module):
                         self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
         return xt, noise
 
-    def _eps(self, x0, cond, t, noise):
-        """the draws of loss() (t, then noise, on self.generator) and the network's eps for them"""
+    def _eps(self, x0, cond, t, noise, keep=None):
+        """the draws of loss() (t, then noise, then -- only in training mode with p_uncond > 0 and no keep given -- the
+        condition dropout keep = rand(B) >= p_uncond, all on self.generator) and the network's eps for them.  keep:
+        bool [B], True = the sample keeps its cond; the others see the null condition (cond zeroed by cesm_cond_mask,
+        whose backward zeroes their d cond).  keep None and nothing drawn: cond goes to the network untouched."""
         B = x0.size(0)
         g = self.generator
         if t is None:
             t = torch.randint(0, self.T, (B,), device=x0.device, generator=g).long()
         if noise is None:
             noise = torch.randn(x0.shape, device=x0.device, dtype=x0.dtype, generator=g)
+        if keep is None and self.p_uncond > 0.0 and self.training:
+            keep = torch.rand(B, device=x0.device, generator=g) >= self.p_uncond
+        if keep is not None:
+            keep = torch.as_tensor(keep, dtype=torch.bool, device=x0.device).contiguous()
+            if tuple(keep.shape) != (B,):
+                raise ValueError(f"keep needs one entry per sample ({B}), got {tuple(keep.shape)}")
+            cond = _CondMask.apply(cond.to(x0.device).float().contiguous(), keep)
         x_t, noise = self.q_sample(x0, t, noise)
         return self.model(x_t, cond, t), noise.float().contiguous(), t
 
-    def loss(self, x0, cond, t=None, noise=None, row0=None):
-        """model.py:203-208; optional t / noise make the draw reproducible for parity tests.  With lat_weight or
-        min_snr_gamma set this is loss_components(...)['total'] (row0: see there), else the plain mean."""
+    def loss(self, x0, cond, t=None, noise=None, row0=None, keep=None):
+        """model.py:203-208; optional t / noise / keep make the draw reproducible for parity tests (keep: _eps).  With
+        lat_weight or min_snr_gamma set this is loss_components(...)['total'] (row0: see there), else the plain mean."""
         if self.weighted:
-            return self.loss_components(x0, cond, t=t, noise=noise, row0=row0)["total"]
-        eps, noise, _ = self._eps(x0, cond, t, noise)
+            return self.loss_components(x0, cond, t=t, noise=noise, row0=row0, keep=keep)["total"]
+        eps, noise, _ = self._eps(x0, cond, t, noise, keep)
         return _MSE.apply(eps, noise)
 
     def lat_weights(self, H, device):
@@ -254,10 +300,11 @@ class Diffusion(nn.Module):
         wrong device row0 gives a wrong loss, never a fault."""
         return check_row0(row0, B, H, Hg, device, has_lat=self._lat is not None)
 
-    def loss_components(self, x0, cond, t=None, noise=None, row0=None):
+    def loss_components(self, x0, cond, t=None, noise=None, row0=None, keep=None):
         """The reference training loop's hook (train.py:836-841): {'mse_raw', 'mse_lat', 'cond_loss', 'total'} as 0-d
         device tensors from one weighted-loss kernel (csrc/misc.hip cesm_wloss; formulas in include/cesm_hip.h).
-        `total` is differentiable; the others are detached, cond_loss is a zero.  RNG use is that of loss().
+        `total` is differentiable; the others are detached, cond_loss is a zero.  RNG use is that of loss(); keep: the
+        condition dropout of loss().
 
         row0: the grid row of each sample's row 0 (crops; DeviceWindowLoader.last_row0), [B]; None: 0.  A list or CPU
         tensor is validated (0 <= row0, row0 + H <= Hg, else ValueError before anything is launched); a CUDA int64
@@ -267,7 +314,7 @@ class Diffusion(nn.Module):
         B, H = x0.shape[0], x0.shape[2]
         w = self.lat_weights(H, x0.device)
         row0 = self._row0(row0, B, H, w.numel(), x0.device)
-        eps, noise, t = self._eps(x0, cond, t, noise)
+        eps, noise, t = self._eps(x0, cond, t, noise, keep)
         a = None if self.min_snr_weight is None else self.min_snr_weight[t]
         raw, lat, total = _WLoss.apply(eps, noise, w, row0, a, self.lat_weight)
         return {"mse_raw": raw, "mse_lat": lat, "cond_loss": torch.zeros((), device=x0.device), "total": total}
@@ -275,12 +322,32 @@ class Diffusion(nn.Module):
     def _coefs(self):
         return self.sqrt_recip_alphas, self.betas, self.sqrt_one_minus_alphas_cumprod, self.posterior_variance
 
+    def _guided_eps(self, x_t, cond, t):
+        """the one network evaluation of a guided step: (x2, eps2) on 2 B rows -- x_t twice, [cond, 0], t twice; rows
+        [0, B) of eps2 are eps(x, cond), rows [B, 2B) eps(x, 0)"""
+        cond = cond.to(x_t.device).float()
+        x2 = torch.cat([x_t, x_t], dim=0)
+        eps2 = self.model(x2, torch.cat([cond, torch.zeros_like(cond)], dim=0), torch.cat([t, t], dim=0))
+        return x2, eps2.float().contiguous()
+
     @torch.no_grad()
-    def p_sample(self, x_t, cond, t, noise=None):
-        """model.py:168-183 (DDPM ancestral step): model evaluation + one fused update kernel."""
+    def p_sample(self, x_t, cond, t, noise=None, guidance_scale=None):
+        """model.py:168-183 (DDPM ancestral step): model evaluation + one fused update kernel.  guidance_scale: see
+        the class docstring (None / 1.0: this step as it was; else one evaluation on 2 B rows and the guided kernel;
+        RNG use does not change)."""
+        gs = check_guidance_scale(guidance_scale)
         with torch.inference_mode():
             x_t = x_t.float().contiguous()
             t = t.to(device=x_t.device, dtype=torch.long).contiguous()
+            if gs is not None:
+                B = x_t.shape[0]
+                t = t.expand(B).contiguous()
+                x2, eps2 = self._guided_eps(x_t, cond, t)
+                if (t == 0).all():
+                    return K.ddpm_step_cfg(x2, eps2, None, t, *self._coefs(), gs)[:B]
+                if noise is None:
+                    noise = torch.randn_like(x_t)
+                return K.ddpm_step_cfg(x2, eps2, noise.float().contiguous(), t, *self._coefs(), gs)[:B]
             eps = self.model(x_t, cond, t).float().contiguous()
             if (t == 0).all():
                 return K.ddpm_step(x_t, eps, None, t, *self._coefs())
@@ -358,20 +425,26 @@ class Diffusion(nn.Module):
         return a, b, sigma
 
     @torch.no_grad()
-    def ddim_step(self, x_t, cond, t, t_prev, eta=0.0, noise=None):
+    def ddim_step(self, x_t, cond, t, t_prev, eta=0.0, noise=None, guidance_scale=None):
         """One generalized DDIM step t -> t_prev (per sample; ddim_coefs has the formula): model evaluation + one
         fused update kernel, the few-step counterpart of p_sample.  Step noise is used (and, without `noise`, drawn
-        with randn_like) only when eta > 0 and some t_prev >= 0."""
+        with randn_like) only when eta > 0 and some t_prev >= 0.  guidance_scale: as p_sample."""
+        gs = check_guidance_scale(guidance_scale)
         with torch.inference_mode():
             x_t = x_t.float().contiguous()
             B = x_t.shape[0]
             t, t_prev, eta = self._ddim_args(t, t_prev, eta)
             t = t.to(x_t.device).expand(B).contiguous()
             t_prev = t_prev.to(x_t.device).expand(B).contiguous()
-            eps = self.model(x_t, cond, t).float().contiguous()
+            if gs is None:
+                eps = self.model(x_t, cond, t).float().contiguous()
+            else:
+                x2, eps2 = self._guided_eps(x_t, cond, t)
             z = None
             if eta > 0.0 and bool((t_prev >= 0).any()):
                 z = (torch.randn_like(x_t) if noise is None else noise.to(x_t.device)).float().contiguous()
+            if gs is not None:
+                return K.ddim_step_cfg(x2, eps2, z, t, t_prev, self.alphas_cumprod, eta, gs)[:B]
             return K.ddim_step(x_t, eps, z, t, t_prev, self.alphas_cumprod, eta)
 
     def _dpmpp_args(self, t, t_prev, t_last):
@@ -421,11 +494,12 @@ class Diffusion(nn.Module):
         return a, b, c, c1, c2
 
     @torch.no_grad()
-    def dpmpp_step(self, x_t, cond, t, t_prev, t_last, x0_last=None):
+    def dpmpp_step(self, x_t, cond, t, t_prev, t_last, x0_last=None, guidance_scale=None):
         """One DPM-Solver++(2M) step t -> t_prev (per sample; dpmpp_coefs has the formula): model evaluation + one
         fused update kernel, the eager counterpart of ddim_step.  Returns (x_prev, x0): x0 is the step's data
         prediction, to be passed as x0_last, with this t as t_last, to the next step.  x0_last is needed where
-        t_last >= 0 and is not read elsewhere; deterministic, draws nothing."""
+        t_last >= 0 and is not read elsewhere; deterministic, draws nothing.  guidance_scale: as p_sample."""
+        gs = check_guidance_scale(guidance_scale)
         with torch.inference_mode():
             x_t = x_t.float().contiguous()
             B = x_t.shape[0]
@@ -434,6 +508,10 @@ class Diffusion(nn.Module):
                 raise ValueError("dpmpp_step: t_last >= 0 needs x0_last, the previous step's x0 estimate")
             if x0_last is not None:
                 x0_last = x0_last.to(x_t.device).float().contiguous()
+            if gs is not None:
+                x2, eps2 = self._guided_eps(x_t, cond, t)
+                x_prev, x0 = K.dpmpp_step_cfg(x2, eps2, x0_last, t, t_prev, t_last, self.alphas_cumprod, gs)
+                return x_prev[:B], x0
             eps = self.model(x_t, cond, t).float().contiguous()
             return K.dpmpp_step(x_t, eps, x0_last, t, t_prev, t_last, self.alphas_cumprod)
 
@@ -460,7 +538,7 @@ class Diffusion(nn.Module):
 
     @torch.no_grad()
     def sample(self, cond, shape, device, use_graph=None, x_T=None, noise_seq=None, steps=None, ddim_eta=0.0,
-               solver="ddim", spacing=None):
+               solver="ddim", spacing=None, guidance_scale=None):
         """model.py:186-194.  On the GPU every p_sample step is ONE replay of a captured HIP graph (the
         F=1 network forward + the fused update); the host only sets t and draws the step noise.  RNG use
         is the reference's: randn(shape) for x_T, then randn_like(x) for every step with t > 0, drawn
@@ -478,13 +556,20 @@ class Diffusion(nn.Module):
         the first and the last also uses the previous step's x0 estimate, at no further network evaluation).  It
         needs steps and ddim_eta == 0, is deterministic (randn(shape) for x_T unless given, nothing else; noise_seq is
         unused), and for executed step k its t_last is the t of step k-1, -1 at k = 0.  spacing picks the time grid
-        (sample_schedule): None means "uniform" for ddim and "logsnr" for dpmpp2m; either may be given to either."""
+        (sample_schedule): None means "uniform" for ddim and "logsnr" for dpmpp2m; either may be given to either.
+
+        guidance_scale=s (classifier-free guidance, every solver, graph and eager): None or exactly 1.0 is the code
+        path above, unchanged; another finite s >= 0 (else ValueError, before anything is captured or launched)
+        evaluates the network once per step on 2 B rows -- x twice, [cond, 0], t twice -- and takes the step with
+        eps(x, 0) + s (eps(x, cond) - eps(x, 0)) in the guided update kernel (cesm_*_step_cfg); s = 0 is the
+        unconditional sampler.  The shapes of x_T, noise_seq and the result and the RNG use are those of the unguided
+        call.  A model trained with p_uncond = 0 never trained its unconditional branch; it is sampled all the same."""
         return self._sample(cond, shape, device, use_graph, x_T, noise_seq, steps, ddim_eta, False, solver=solver,
-                            spacing=spacing)
+                            spacing=spacing, guidance_scale=guidance_scale)
 
     @torch.no_grad()
     def sample_ensemble(self, cond, members, device=None, steps=None, ddim_eta=0.0, member_batch=None, x_T=None,
-                        noise_seq=None, use_graph=None, solver="ddim", spacing=None):
+                        noise_seq=None, use_graph=None, solver="ddim", spacing=None, guidance_scale=None):
         """`members` samples for every row of cond: [B, M, V, H, W] fp32 (cond [B, V, H, W] or a window
         [B, V, Fc, H, W]).  The B M jobs, b-major (job b M + m is member m of cond[b]), run in chunks of at most
         member_batch network samples (default: all in one chunk); each chunk goes through sample()'s loop with
@@ -495,12 +580,15 @@ class Diffusion(nn.Module):
         steps / ddim_eta / use_graph / solver / spacing: as sample().  RNG use, chunk by chunk: randn for the chunk's
         x_T, then that chunk's step noise exactly as sample() documents, then the next chunk.  Test hooks: x_T [B, M, V, H, W] and
         noise_seq [N, B, M, V, H, W] replace the draws, sliced per chunk; with them a chunk equals, bit for bit,
-        sample(cond.repeat_interleave(M, 0)[chunk], ..., x_T=..., noise_seq=...) on the same rows."""
+        sample(cond.repeat_interleave(M, 0)[chunk], ..., x_T=..., noise_seq=...) on the same rows.
+
+        guidance_scale: as sample().  member_batch still counts fields; with guidance the network batch of a chunk is
+        twice that."""
         return self._sample_ensemble(cond, members, device, steps, ddim_eta, member_batch, x_T, noise_seq, use_graph,
-                                     False, solver=solver, spacing=spacing)
+                                     False, solver=solver, spacing=spacing, guidance_scale=guidance_scale)
 
     def _sample_ensemble(self, cond, members, device, steps, ddim_eta, member_batch, x_T, noise_seq, use_graph, paired,
-                         solver="ddim", spacing=None):
+                         solver="ddim", spacing=None, guidance_scale=None):
         """sample_ensemble(); paired: cond is two halves [cond, cond2] whose jobs b M + m get the same x_T and step
         noise (one chunk only: counterfactual_delta)"""
         if cond.ndim not in (4, 5):
@@ -523,6 +611,7 @@ class Diffusion(nn.Module):
         if use_graph is None:
             use_graph = os.environ.get("CESM_SAMPLE_GRAPH", "1") != "0"
         self._sample_grid(steps, ddim_eta, solver, spacing)  # range checks before anything is captured
+        check_guidance_scale(guidance_scale)
         eta = None if steps is None else float(ddim_eta)
         with torch.inference_mode():
             cond = cond.to(device)
@@ -540,20 +629,24 @@ class Diffusion(nn.Module):
                     step = captured.get(n)
                     if step is None:
                         step = captured[n] = GraphSampleStep(self, c, torch.zeros((n, V, H, W), device=device),
-                                                             ddim_eta=eta, solver=solver)
+                                                             ddim_eta=eta, solver=solver,
+                                                             guidance_scale=guidance_scale)
                 x = self._sample(c, (n, V, H, W), device, use_graph, None if xT is None else xT[j0:j1],
                                  None if ns is None else ns[:, j0:j1], steps, ddim_eta, paired, step=step,
-                                 solver=solver, spacing=spacing)
+                                 solver=solver, spacing=spacing, guidance_scale=guidance_scale)
                 flat[j0:j1].copy_(x)
             return out
 
     def _sample(self, cond, shape, device, use_graph, x_T, noise_seq, steps, ddim_eta, paired, step=None,
-                solver="ddim", spacing=None):
+                solver="ddim", spacing=None, guidance_scale=None):
         """sample(); paired: the batch is two halves that get the same x_T and the same step noise (drawn for one
         half, copied to the other: counterfactual_delta).  step: a GraphSampleStep captured earlier for this batch
-        size, ddim_eta and solver (sample_ensemble); the graph path then loads cond and x_T into its static buffers
-        instead of capturing a new one, and the result is that step's x buffer (valid until the step runs again)."""
+        size, ddim_eta, solver and guidance_scale (sample_ensemble); the graph path then loads cond and x_T into its
+        static buffers instead of capturing a new one, and the result is that step's x buffer (valid until the step
+        runs again).  guidance_scale: sample(); the guidance halves stay inside the steps, the paired halves are rows
+        of the B-row batch."""
         tau, ddim_eta = self._sample_grid(steps, ddim_eta, solver, spacing)
+        gs = check_guidance_scale(guidance_scale)
         if paired and shape[0] % 2:
             raise ValueError("paired sampling needs an even batch")
 
@@ -585,10 +678,10 @@ class Diffusion(nn.Module):
                         x0 = None
                         for (tt, tp), tl in zip(pairs, lasts):
                             tt, tp, tl = (torch.full((B,), v, device=device, dtype=torch.long) for v in (tt, tp, tl))
-                            x, x0 = self.dpmpp_step(x, cond, tt, tp, tl, x0)
+                            x, x0 = self.dpmpp_step(x, cond, tt, tp, tl, x0, guidance_scale=gs)
                         return x
                     if step is None:
-                        step = GraphSampleStep(self, cond, x, ddim_eta=0.0, solver=solver)
+                        step = GraphSampleStep(self, cond, x, ddim_eta=0.0, solver=solver, guidance_scale=gs)
                     else:
                         step.load(cond, x)
                     for (tt, tp), tl in zip(pairs, lasts):
@@ -602,10 +695,10 @@ class Diffusion(nn.Module):
                         nz = None
                         if noisy and tp >= 0:
                             nz = noise_seq[k].to(device) if noise_seq is not None else randn()
-                        x = self.ddim_step(x, cond, t_tensor, tp_tensor, ddim_eta, noise=nz)
+                        x = self.ddim_step(x, cond, t_tensor, tp_tensor, ddim_eta, noise=nz, guidance_scale=gs)
                     return x
                 if step is None:
-                    step = GraphSampleStep(self, cond, x, ddim_eta=ddim_eta)
+                    step = GraphSampleStep(self, cond, x, ddim_eta=ddim_eta, guidance_scale=gs)
                 else:
                     step.load(cond, x)
                 for k, (tt, tp) in enumerate(pairs):
@@ -622,10 +715,10 @@ class Diffusion(nn.Module):
                     nz = None if noise_seq is None or tt == 0 else noise_seq[i].to(device)
                     if paired and nz is None and tt != 0:
                         nz = randn()
-                    x = self.p_sample(x, cond, t_tensor, noise=nz)
+                    x = self.p_sample(x, cond, t_tensor, noise=nz, guidance_scale=gs)
                 return x
             if step is None:
-                step = GraphSampleStep(self, cond, x)
+                step = GraphSampleStep(self, cond, x, guidance_scale=gs)
             else:
                 step.load(cond, x)
             for i, tt in enumerate(reversed(range(self.T))):
@@ -652,10 +745,17 @@ class GraphSampleStep:
     solver="dpmpp2m" (ddim_eta None or 0) captures the DPM-Solver++(2M) step (Diffusion.dpmpp_step) in place on x and
     on a static history buffer x0_last, which every replay overwrites with its x0 estimate: t_prev and t_last are
     static inputs, run(tt, tt_prev, tt_last) sets all three, and there is no noise buffer.  A step with tt_last = -1
-    does not read the history, so load() leaves it as it is."""
+    does not read the history, so load() leaves it as it is.
 
-    def __init__(self, diffusion, cond, x, ddim_eta=None, solver="ddim"):
+    guidance_scale (None or 1.0: everything above, unchanged) captures the guided step instead: the step owns
+    x2 [2B, ...], cond2 [2B, ...] and t2 [2B]; x, cond and t are their leading-B views, so callers read step.x as ever.
+    The network runs once on the 2B rows and the guided update kernel writes x_prev into both halves of x2.  cond2's
+    second half (the null condition) is zero from construction and never written again; load() writes x into both
+    halves; z, x0_last, t_prev and t_last stay B-sized.  The scale is passed by value and fixed at capture."""
+
+    def __init__(self, diffusion, cond, x, ddim_eta=None, solver="ddim", guidance_scale=None):
         self.d = diffusion
+        self.scale = check_guidance_scale(guidance_scale)
         if solver not in ("ddim", "dpmpp2m"):
             raise ValueError(f"solver must be 'ddim' or 'dpmpp2m', got {solver!r}")
         self.multistep = solver == "dpmpp2m"
@@ -666,9 +766,18 @@ class GraphSampleStep:
         self.eta = None if ddim_eta is None else float(ddim_eta)
         if self.eta is not None and not self.eta >= 0.0:
             raise ValueError(f"ddim_eta must be >= 0, got {ddim_eta}")
-        self.x = x.float().contiguous()
-        self.cond = cond.float().contiguous()
-        self.t = torch.zeros(x.shape[0], dtype=torch.long, device=x.device)
+        if self.scale is None:
+            self.x = x.float().contiguous()
+            self.cond = cond.float().contiguous()
+            self.t = torch.zeros(x.shape[0], dtype=torch.long, device=x.device)
+            self.x2 = self.cond2 = self.t2 = None
+        else:
+            B = x.shape[0]
+            x, cond = x.float(), cond.to(x.device).float()
+            self.x2 = torch.cat([x, x], dim=0)
+            self.cond2 = torch.cat([cond, torch.zeros_like(cond)], dim=0)
+            self.t2 = torch.zeros(2 * B, dtype=torch.long, device=x.device)
+            self.x, self.cond, self.t = self.x2[:B], self.cond2[:B], self.t2[:B]
         self.t_prev = None if self.eta is None else torch.full_like(self.t, -1)
         self.t_last = torch.full_like(self.t, -1) if self.multistep else None
         self.x0_last = torch.zeros_like(self.x) if self.multistep else None
@@ -680,7 +789,7 @@ class GraphSampleStep:
             for _ in range(2):
                 self._step()
         torch.cuda.current_stream().wait_stream(side)
-        self.x.copy_(x0)
+        self._put_x(x0)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self._step()
@@ -691,10 +800,28 @@ class GraphSampleStep:
         if tuple(x.shape) != tuple(self.x.shape) or tuple(cond.shape) != tuple(self.cond.shape):
             raise ValueError(f"GraphSampleStep captured for x {tuple(self.x.shape)} and cond {tuple(self.cond.shape)}, "
                              f"got {tuple(x.shape)} and {tuple(cond.shape)}")
-        self.x.copy_(x)
+        self._put_x(x)
         self.cond.copy_(cond)
 
+    def _put_x(self, x):
+        self.x.copy_(x)
+        if self.scale is not None:
+            self.x2[self.x.shape[0]:].copy_(x)
+
+    def _step_guided(self):
+        d, s = self.d, self.scale
+        eps = d.model(self.x2, self.cond2, self.t2).float().contiguous()
+        if self.eta is None:
+            K.ddpm_step_cfg(self.x2, eps, self.z, self.t, *d._coefs(), s, out=self.x2)
+        elif self.multistep:
+            K.dpmpp_step_cfg(self.x2, eps, self.x0_last, self.t, self.t_prev, self.t_last, d.alphas_cumprod, s,
+                             out=self.x2, x0_out=self.x0_last)
+        else:
+            K.ddim_step_cfg(self.x2, eps, self.z, self.t, self.t_prev, d.alphas_cumprod, self.eta, s, out=self.x2)
+
     def _step(self):
+        if self.scale is not None:
+            return self._step_guided()
         eps = self.d.model(self.x, self.cond, self.t).float().contiguous()
         if self.eta is None:
             K.ddpm_step(self.x, eps, self.z, self.t, *self.d._coefs(), out=self.x)
@@ -715,7 +842,7 @@ class GraphSampleStep:
             raise ValueError(f"step indices out of range: t = {tt}, t_prev = {tt_prev}, T = {self.d.T}")
         if tt_last is not None and not (tt_last == -1 or tt < tt_last < self.d.T):
             raise ValueError(f"step indices out of range: t = {tt}, t_last = {tt_last}, T = {self.d.T}")
-        self.t.fill_(tt)
+        (self.t if self.scale is None else self.t2).fill_(tt)
         if tt_prev is not None:
             self.t_prev.fill_(tt_prev)
         if tt_last is not None:

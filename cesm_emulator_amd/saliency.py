@@ -11,14 +11,16 @@ from __future__ import annotations
 
 import torch
 
-from .model import _MSE
+from .model import _CondMask, _MSE
 from .video_net import input_grads_only
 
 
-def input_grads(diffusion, x0, cond, t=None, noise=None):
+def input_grads(diffusion, x0, cond, t=None, noise=None, keep=None):
     """(loss, d loss / d x_t, d loss / d cond) of the eps-prediction MSE at x_t = q_sample(x0, t, noise).
     x0 [B,V,H,W]; cond [B,V,H,W] (F = 1) or a window [B,V,F,H,W]; t defaults to T // 2 for every sample.  The
-    gradients have x_t's (= x0's) and cond's shapes and are fp32; loss is detached."""
+    gradients have x_t's (= x0's) and cond's shapes and are fp32; loss is detached.  keep (bool [B], the condition
+    dropout of Diffusion.loss): the samples with keep False see the null condition, and their d cond is exactly zero;
+    nothing is drawn here, whatever the diffusion's p_uncond."""
     B = x0.size(0)
     if t is None:
         t = torch.full((B,), diffusion.T // 2, device=x0.device, dtype=torch.long)
@@ -26,7 +28,13 @@ def input_grads(diffusion, x0, cond, t=None, noise=None):
         x_t, noise = diffusion.q_sample(x0.detach(), t, noise)
         x_req = x_t.detach().requires_grad_(True)
         cond_req = cond.detach().clone().requires_grad_(True)
-        eps = diffusion.model(x_req, cond_req, t)
+        cond_in = cond_req
+        if keep is not None:
+            keep = torch.as_tensor(keep, dtype=torch.bool, device=x0.device).contiguous()
+            if tuple(keep.shape) != (B,):
+                raise ValueError(f"keep needs one entry per sample ({B}), got {tuple(keep.shape)}")
+            cond_in = _CondMask.apply(cond_req.float().contiguous(), keep)
+        eps = diffusion.model(x_req, cond_in, t)
         loss = _MSE.apply(eps, noise.float().contiguous())
         with input_grads_only():
             dxt, dcond = torch.autograd.grad(loss, (x_req, cond_req))
@@ -34,10 +42,11 @@ def input_grads(diffusion, x0, cond, t=None, noise=None):
 
 
 def counterfactual_delta(diffusion, cond, scale_mask=None, scale=1.1, steps=None, ddim_eta=0.0, paired=False,
-                         n_samples=1, solver="ddim", spacing=None):
+                         n_samples=1, solver="ddim", spacing=None, guidance_scale=None):
     """Sampled response to scaled emissions (the reference's train.py counterfactual_delta): sample(cond2) -
     sample(cond) with cond2 = cond * scale, or cond * (1 + (scale - 1) * scale_mask) where a mask is given.  steps,
-    ddim_eta, solver and spacing go to Diffusion.sample (steps=None: the full ancestral loop).
+    ddim_eta, solver, spacing and guidance_scale go to Diffusion.sample (steps=None: the full ancestral loop; with
+    guidance the paired halves are rows of the batch and the guidance halves stay inside the steps).
 
     Default: two sampling runs, base first, each drawing its own x_T and step noise (the reference's semantics), so
     the difference also carries the sampling noise.  paired=True: ONE run of batch 2B over [cond, cond2] in which both
@@ -53,7 +62,7 @@ def counterfactual_delta(diffusion, cond, scale_mask=None, scale=1.1, steps=None
         raise ValueError(f"n_samples must be >= 1, got {n_samples}")
     cond2 = cond * scale if scale_mask is None else cond * (1.0 + (scale - 1.0) * scale_mask)
     B, V, H, W = cond.shape[0], cond.shape[1], cond.shape[-2], cond.shape[-1]  # V target variables, as cond has
-    kw = dict(solver=solver, spacing=spacing)
+    kw = dict(solver=solver, spacing=spacing, guidance_scale=guidance_scale)
     if n_samples > 1:
         if paired:
             x = diffusion._sample_ensemble(torch.cat([cond, cond2], dim=0), n_samples, cond.device, steps, ddim_eta,
@@ -71,10 +80,10 @@ def counterfactual_delta(diffusion, cond, scale_mask=None, scale=1.1, steps=None
     return pert - base
 
 
-def saliency_wrt_cond(diffusion, x0, cond, t=None, noise=None, normalize=True):
+def saliency_wrt_cond(diffusion, x0, cond, t=None, noise=None, normalize=True, keep=None):
     """|d loss / d cond| in cond's shape (the reference's train.py saliency_wrt_cond); with normalize, every sample's
-    map(s) divided by its spatial maximum + 1e-8."""
-    g = input_grads(diffusion, x0, cond, t, noise)[2].abs()
+    map(s) divided by its spatial maximum + 1e-8.  keep: as input_grads (a dropped sample's map is all zero)."""
+    g = input_grads(diffusion, x0, cond, t, noise, keep=keep)[2].abs()
     if normalize:
         g = g / (g.amax(dim=(-2, -1), keepdim=True) + 1e-8)
     return g

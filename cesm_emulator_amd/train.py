@@ -15,7 +15,7 @@ import contextlib
 
 import torch
 
-from .model import UNet, Diffusion
+from .model import UNet, Diffusion, check_guidance_scale
 from .optim import FusedAdamW
 from .ema import EMA
 from .ensemble import EnsembleVerifier
@@ -77,10 +77,23 @@ def make_ema(diffusion, optimizer, train_cfg):
     return EMA(diffusion.model, optimizer, beta=cfg.get("beta", 0.9999), warmup=cfg.get("warmup", True))
 
 
+def guidance_p_uncond(train_cfg):
+    """p_uncond of train_cfg["guidance"] = {"p_uncond": p} (0.0 without the block); strict keys"""
+    cfg = train_cfg.get("guidance") or {}
+    if not isinstance(cfg, dict):
+        raise TypeError(f"train.guidance must be a mapping with p_uncond, got {cfg!r}")
+    unknown = sorted(set(cfg) - {"p_uncond"})
+    if unknown:
+        raise ValueError(f"train.guidance: unknown keys {unknown} (p_uncond)")
+    return cfg.get("p_uncond", 0.0)
+
+
 def make_diffusion(unet, train_cfg, lat=None):
-    """The Diffusion of a training config: `timesteps`, `beta_schedule` and an optional
-    train_cfg["loss"] = {"lat_weight": …, "min_snr_gamma": …} (the weighted loss; the shipped configs do not set it).
-    lat: latitudes in degrees of the full grid's rows, from the data (Diffusion's `lat`)."""
+    """The Diffusion of a training config: `timesteps`, `beta_schedule`, an optional
+    train_cfg["loss"] = {"lat_weight": …, "min_snr_gamma": …} (the weighted loss) and an optional
+    train_cfg["guidance"] = {"p_uncond": p} (condition dropout for classifier-free guidance; Diffusion's `p_uncond`).
+    The shipped configs set neither.  lat: latitudes in degrees of the full grid's rows, from the data (Diffusion's
+    `lat`)."""
     cfg = train_cfg.get("loss") or {}
     if not isinstance(cfg, dict):
         raise TypeError(f"train.loss must be a mapping with lat_weight / min_snr_gamma, got {cfg!r}")
@@ -89,15 +102,16 @@ def make_diffusion(unet, train_cfg, lat=None):
         raise ValueError(f"train.loss: unknown keys {unknown} (lat_weight, min_snr_gamma)")
     return Diffusion(unet, img_channels=1, timesteps=train_cfg.get("timesteps", 1000),
                      beta_schedule=train_cfg.get("beta_schedule", "linear"), lat_weight=cfg.get("lat_weight", 0.0),
-                     min_snr_gamma=cfg.get("min_snr_gamma"), lat=lat)
+                     min_snr_gamma=cfg.get("min_snr_gamma"), lat=lat, p_uncond=guidance_p_uncond(train_cfg))
 
 
 def train_step(diffusion, optimizer, x0, cond, max_grad_norm=1.0, dp=None, t=None, noise=None, row0=None,
-               return_components=False):
+               return_components=False, keep=None):
     """One optimizer step; returns the loss as a device tensor (no host sync).  row0: the batch's crop row offsets
     for a weighted loss (Diffusion.loss_components).  return_components=True returns (loss, comps) instead, comps a
     [4] device tensor ordered mse_raw, mse_lat, cond_loss, total (the plain loss: loss, loss, 0, loss); the step is
-    taken on total either way."""
+    taken on total either way.  keep: the condition dropout of Diffusion.loss (bool [B]; None: drawn there when the
+    diffusion has p_uncond > 0)."""
     optimizer.zero_grad(set_to_none=True)
     net = diffusion.model.net
     overlap = dp is not None and getattr(dp, "overlap", True)
@@ -105,13 +119,13 @@ def train_step(diffusion, optimizer, x0, cond, max_grad_norm=1.0, dp=None, t=Non
         dp.arm(net, optimizer.flat)  # bucket all-reduces issued during the backward
     comps = None
     if not return_components:
-        loss = diffusion.loss(x0, cond, t=t, noise=noise, row0=row0)
+        loss = diffusion.loss(x0, cond, t=t, noise=noise, row0=row0, keep=keep)
     elif diffusion.weighted:
-        c = diffusion.loss_components(x0, cond, t=t, noise=noise, row0=row0)
+        c = diffusion.loss_components(x0, cond, t=t, noise=noise, row0=row0, keep=keep)
         loss = c["total"]
         comps = torch.stack([c["mse_raw"], c["mse_lat"], c["cond_loss"], loss.detach()])
     else:
-        loss = diffusion.loss(x0, cond, t=t, noise=noise)
+        loss = diffusion.loss(x0, cond, t=t, noise=noise, keep=keep)
         comps = torch.stack([loss.detach(), loss.detach(), torch.zeros_like(loss), loss.detach()])
     loss.backward()
     if overlap:
@@ -169,15 +183,16 @@ def train_one_epoch(diffusion, dl, optimizer, device, max_grad_norm=1.0, use_amp
 
 
 def validate_ensemble(diffusion, loader, members, steps=None, ddim_eta=0.0, member_batch=None, max_batches=None,
-                      ema=None, norm=None, solver="ddim", spacing=None):
+                      ema=None, norm=None, solver="ddim", spacing=None, guidance_scale=None):
     """Ensemble verification over a loader of (cond, target) batches: per batch, `members` samples per condition
-    (Diffusion.sample_ensemble with steps / ddim_eta / member_batch / solver / spacing) are judged against the loader's
-    target with the batch's crop row offsets (`loader.last_row0`; a loader without it: no crop), all batches accumulated on the device
+    (Diffusion.sample_ensemble with steps / ddim_eta / member_batch / solver / spacing / guidance_scale) are judged
+    against the loader's target with the batch's crop row offsets (`loader.last_row0`; a loader without it: no crop), all batches accumulated on the device
     (ensemble.EnsembleVerifier, one kernel call per batch, no host synchronisation).  Returns the verifier's result():
     per-variable mse, rmse, var, spread, ssr, crps and rank_hist, area-weighted with the diffusion's `lat` (uniform
     weights without one).  ema: an ema.EMA; sampling then runs under ema.applied(diffusion).  max_batches: stop after
     that many batches.  RNG use is sample_ensemble's, batch after batch.  norm (data.load_fields' statistics): the
     per-variable results in physical units (EnsembleVerifier.result(norm=))."""
+    check_guidance_scale(guidance_scale)  # before the loader is touched
     verifier = None
     with (ema.applied(diffusion) if ema is not None else contextlib.nullcontext()):
         for k, (cond, x0) in enumerate(loader):
@@ -189,7 +204,7 @@ def validate_ensemble(diffusion, loader, members, steps=None, ddim_eta=0.0, memb
             if verifier is None:
                 verifier = EnsembleVerifier(members, x0.shape[1], lat=diffusion._lat, device=device)
             ens = diffusion.sample_ensemble(cond, members, steps=steps, ddim_eta=ddim_eta, member_batch=member_batch,
-                                            solver=solver, spacing=spacing)
+                                            solver=solver, spacing=spacing, guidance_scale=guidance_scale)
             verifier.update(ens, x0, row0=row0)
     if verifier is None:
         raise ValueError("validate_ensemble: the loader gave no batch")

@@ -411,6 +411,34 @@ int cesm_ddim_step(const float* x, const float* eps, const float* z, const int64
 int cesm_dpmpp_step(const float* x, const float* eps, const float* x0_last, const int64_t* t, const int64_t* t_prev,
                     const int64_t* t_last, const float* alphas_cumprod, float* out, float* x0_out, int B, int64_t HW,
                     int T, hipStream_t stream);
+/* Classifier-free guidance (Ho & Salimans 2022): the three updates above with the combine of a conditional and an
+ * unconditional network evaluation fused in,
+ *   g = eps_u + scale (eps_c - eps_u),  formed as fma(scale, eps_c - eps_u, eps_u): one rounded subtraction, one FMA;
+ * everything after it is the unguided kernel's own code with g in the place of eps (equal halves, eps_u == eps_c, give
+ * the unguided result bit for bit at every scale).  Arguments are those of the unguided entry plus `scale`, a finite
+ * number >= 0 (1: the conditional model, 0: the unconditional one).  B counts SAMPLES; x, eps and out have 2 B rows:
+ * rows [0, B) of eps are eps_c (evaluated on cond), rows [B, 2B) eps_u (evaluated on the null condition, an all-zero
+ * cond); x is read from rows [0, B) only, and x_prev is written to row b and to row b + B, so the next network
+ * evaluation finds both halves equal without a copy.  z, x0_last, x0_out, t, t_prev and t_last have B rows / entries.
+ * Aliasing, null z / x0_last, index clamps, the 16-byte path and the B / HW / T checks: as the unguided entries.
+ * CESM_EINVAL also on a scale that is negative or not finite and on a null pointer (z and x0_last apart).
+ * Added entry points (no existing argument list changed): the ABI version stays, as for cesm_ddim_step. */
+int cesm_ddpm_step_cfg(const float* x, const float* eps, const float* z, const int64_t* t,
+                       const float* sqrt_recip_alphas, const float* betas, const float* sqrt_one_minus_ac,
+                       const float* posterior_variance, float* out, int B, int64_t HW, float scale,
+                       hipStream_t stream);
+int cesm_ddim_step_cfg(const float* x, const float* eps, const float* z, const int64_t* t, const int64_t* t_prev,
+                       const float* alphas_cumprod, float eta, float* out, int B, int64_t HW, int T, float scale,
+                       hipStream_t stream);
+int cesm_dpmpp_step_cfg(const float* x, const float* eps, const float* x0_last, const int64_t* t,
+                        const int64_t* t_prev, const int64_t* t_last, const float* alphas_cumprod, float* out,
+                        float* x0_out, int B, int64_t HW, int T, float scale, hipStream_t stream);
+/* Condition dropout of guidance training: out[b][:] = keep[b] ? cond[b][:] : 0 for b < B.  cond, out: [B][n] fp32, n
+ * the elements of one sample ([V][H][W] or a window [V][Fc][H][W]); keep: [B] bytes (a torch.bool tensor), non-zero
+ * keeps.  A select, not a multiply: a dropped sample's cond is not read, so a NaN or Inf there does not reach out, and
+ * its out is +0.  out may alias cond.  16-byte accesses where n % 4 == 0 and both are 16-byte aligned, else one element
+ * per access.  CESM_EINVAL on a null pointer, B < 1, B > 65535 or n < 1. */
+int cesm_cond_mask(const float* cond, const unsigned char* keep, float* out, int B, int64_t n, hipStream_t stream);
 int cesm_mse(const float* pred, const float* tgt, float* loss, float* part, int64_t n, hipStream_t stream);
 int cesm_mse_bwd(const float* pred, const float* tgt, const float* gscale, float* dpred, int64_t n,
                  hipStream_t stream);
