@@ -1132,6 +1132,17 @@ static TfDq tf_dq_kind(int nt, int F) { return nt >= 2 || F >= 8 ? TF_FUSED : TF
 
 extern "C" {
 
+// ND of the tflash_bwd_fused_kernel<NT, ND> cesm_tflash_bwd instantiates for (F, num_buckets, max_distance): NT - 1
+// exact bias-gradient diagonals per side, or for NT >= 4 the saturated form ND = 2 when every offset beyond two
+// diagonals shares the bucket of +-(F - 1); -1 when no fused kernel runs (the two-kernel form at F < 8, or F
+// unsupported).  Host-only query; the launcher below dispatches on this same value.
+int cesm_tflash_bwd_nd(int F, int num_buckets, int max_distance) {
+  if (F < 1 || F > 16 * TF_MAXT) return -1;
+  const int nt = (F + 15) / 16;
+  if (tf_dq_kind(nt, F) != TF_FUSED) return -1;
+  return nt >= 4 && tfb_nd(F, nt, num_buckets, max_distance) <= 2 ? 2 : nt - 1;
+}
+
 // name of the dq kernel cesm_tflash_bwd runs for (F, HW) with frame-major qkv (host-only query; "invalid" when F
 // is unsupported)
 const char* cesm_tflash_bwd_variant(int F, int HW) {
@@ -1195,7 +1206,7 @@ int cesm_tflash_bwd(const void* qkv, const void* o, const void* dout, const floa
   if (kind == TF_FUSED) {
     if ((int64_t)16 * (pm ? 1 : HW) * QKV * 2 >= (1ll << 31))
       return CESM_EUNSUPPORTED;  // 32-bit lane offsets of a 16-row tile
-    const int nd = tfb_nd(F, nt, num_buckets, max_distance);
+    const int nd = cesm_tflash_bwd_nd(F, num_buckets, max_distance);
     const size_t sm = tfb_smem(F, nt);
     dim3 gf(4 * TFB_NB, B);
     float* pt = dtable ? part : nullptr;
@@ -1205,8 +1216,8 @@ int cesm_tflash_bwd(const void* qkv, const void* o, const void* dout, const floa
     tflash_bwd_fused_kernel<N, D><<<gf, 256, sm, stream>>>((const bf16*)qkv, (const bf16*)o, (const bf16*)dout, lse, \
                                                            bias, rot, (bf16*)dqkv, pt, F, HW, scale, pm);            \
   }
-#define TFUN(N)                           \
-  if (N >= 4 && nd <= 2) TFU(N, (N >= 4 ? 2 : N - 1)) \
+#define TFUN(N)         \
+  if (nd == 2) TFU(N, 2) \
   else TFU(N, N - 1)
     switch (nt) {
       case 1: TFU(1, 0); break;

@@ -261,6 +261,10 @@ int cesm_tflash_nblk(int HW);
 /* name of the backward kernel (the fused one, or the dq kernel of the two-kernel form) cesm_tflash_bwd runs for
  * (F, HW) (host-only query) */
 const char* cesm_tflash_bwd_variant(int F, int HW);
+/* ND of the tflash_bwd_fused_kernel<NT, ND> cesm_tflash_bwd instantiates (NT = ceil(F / 16)): NT - 1 exact
+ * bias-gradient diagonals per side, or 2 (saturated accumulators) for NT >= 4 when every offset beyond two diagonals
+ * falls into the bucket of +-(F - 1); -1 when no fused kernel runs (F < 8, or F unsupported).  Host-only query. */
+int cesm_tflash_bwd_nd(int F, int num_buckets, int max_distance);
 /* qkv_pixel_major (F > 16): qkv / dqkv rows ordered [B][HW][F] (a pixel's frames adjacent: the long-window path's
  * LN writes its output in that order, so the to_qkv GEMM produces it); out / dout / lse keep their layouts */
 int cesm_tflash_fwd(const void* qkv, const float* bias, const float* rot, void* out, float* lse, int B, int F, int HW,

@@ -279,7 +279,9 @@ def ln_slice_ids(V, perm, output_order, device="cpu"):
 
 # ---------------------------------------------------------------------------------------------- judging
 class Verdict:
-    """worst figures of one judged result: ratio = err / tol (passes iff <= 1), err and the e32 that went with it"""
+    """worst figures of one judged result: ratio = err / tol (passes iff <= 1), err and the e32 that went with it
+    (ename: what the reference's own error is called in print; tests/attn_ref.py's bf16 mode sets e16)"""
+    ename = "e32"
 
     def __init__(self, name, ratio, err, e32, what):
         self.name, self.what = name, what
@@ -290,7 +292,7 @@ class Verdict:
         return self.ratio <= 1.0 and math.isfinite(self.ratio)
 
     def __str__(self):
-        return f"{self.name}: err/tol {self.ratio:.3g} err {self.err:.3g} e32 {self.e32:.3g} ({self.what})"
+        return f"{self.name}: err/tol {self.ratio:.3g} err {self.err:.3g} {self.ename} {self.e32:.3g} ({self.what})"
 
 
 def _scatter(vals, sid, n, reduce):
@@ -370,11 +372,11 @@ def whole_l2(k, r):
     return (torch.linalg.vector_norm(k.double() - r) / torch.linalg.vector_norm(r).clamp_min(1e-30)).item()
 
 
-def report(tag, verdicts):
-    """print every verdict and the worst on one line (the GPU run's lines are kept in profiles/norm_parity.txt), then
-    assert them all"""
+def report(tag, verdicts, prefix="norm_parity"):
+    """print every verdict and the worst on one line (the GPU run's lines are kept in profiles/norm_parity.txt;
+    tests/attn_ref.py prints with the prefix attn_parity), then assert them all"""
     worst = max(verdicts, key=lambda v: v.ratio if math.isfinite(v.ratio) else float("inf"))
-    print(f"norm_parity {tag}: worst err/tol {worst.ratio:.3g} err {worst.err:.3g} e32 {worst.e32:.3g} [{worst.name}, "
-          f"{worst.what}]")
+    print(f"{prefix} {tag}: worst err/tol {worst.ratio:.3g} err {worst.err:.3g} {worst.ename} {worst.e32:.3g} "
+          f"[{worst.name}, {worst.what}]")
     bad = [str(v) for v in verdicts if not v.ok]
     assert not bad, f"{tag}: " + "; ".join(bad)
