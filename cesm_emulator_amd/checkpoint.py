@@ -74,7 +74,8 @@ def build_from_config(cfg, device):
                 base_ch=unet_cfg.get("base_ch", 64), ch_mults=tuple(unet_cfg.get("ch_mults", (1, 2, 4))),
                 num_res_blocks=unet_cfg.get("num_res_blocks", 2), time_dim=unet_cfg.get("time_dim", 256),
                 groups=unet_cfg.get("groups", 8), dropout=unet_cfg.get("dropout", 0.0),
-                use_temp_attn=unet_cfg.get("use_temp_attn", True)).to(device)
+                use_temp_attn=unet_cfg.get("use_temp_attn", True),
+                cond_channels=unet_cfg.get("cond_channels")).to(device)
     diffusion = Diffusion(unet, img_channels=1, timesteps=train_cfg.get("timesteps", 1000),
                           beta_schedule=train_cfg.get("beta_schedule", "linear"),
                           p_uncond=guidance_p_uncond(train_cfg)).to(device)

@@ -813,6 +813,67 @@ __global__ __launch_bounds__(256) void window_gather_mv_kernel(const float* __re
   }
 }
 
+// cesm_window_gather_mc: the kernel above with the cond plane count Cc separated from V (cwin [n][Cc][K][h][w], x0
+// [n][V][h][w]; work units (n, plane in Cc K + V, y)).  A kernel of its own, so that the one above stays as it is.
+template <bool VEC>
+__global__ __launch_bounds__(256) void window_gather_mc_kernel(const float* __restrict__ cond,
+                                                               const float* __restrict__ tgt,
+                                                               const int64_t* __restrict__ times,
+                                                               const int64_t* __restrict__ meta,
+                                                               float* __restrict__ cwin, float* __restrict__ x0,
+                                                               GatherSel sel, int64_t R, int K, int V, int Cc, int Vc,
+                                                               int T, int M, int H, int W, int h, int w, int L) {
+  const int slot = (int)threadIdx.x / L, li = (int)threadIdx.x - slot * L, slots = 256 / L;
+  if (slot >= slots) return;
+  const int CK = Cc * K, P = CK + V;
+  for (int64_t r = (int64_t)blockIdx.x * slots + slot; r < R; r += (int64_t)gridDim.x * slots) {
+    const int64_t np = row_div(r, h);
+    const int y = (int)(r - np * h);
+    const int64_t n = row_div(np, P);
+    const int p = (int)(np - n * P);
+    const int64_t* mt = meta + n * 4;  // (member, anchor, i, j)
+    const int64_t m = clamp_i64(mt[0], M - 1);
+    const int64_t i = clamp_i64(mt[2], H - h), j = clamp_i64(mt[3], W - w);
+    const float* src;
+    float* dst;
+    int64_t t, plane;
+    if (p < CK) {
+      const int v = p / K, k = p - v * K;
+      const int c = v == 0 ? sel.c0 : v == 1 ? sel.c1 : v == 2 ? sel.c2 : sel.c3;
+      t = times[n * K + k];
+      plane = (int64_t)Vc;
+      src = cond + (int64_t)c * H * W;
+      dst = cwin + ((n * CK + p) * h + y) * w;
+    } else {
+      const int v = p - CK;
+      t = mt[1];
+      plane = (int64_t)V;
+      src = tgt + (int64_t)v * H * W;
+      dst = x0 + ((n * V + v) * h + y) * w;
+    }
+    t = clamp_i64(t, T - 1);
+    src += ((t * M + m) * plane * H + i + y) * W + j;
+    if (VEC) {
+      // 16-byte stores to aligned rows; 16-byte loads only where this source row happens to be aligned
+      if (((uintptr_t)src & 15) == 0) {
+        for (int e = li; e < (w >> 2); e += L) {
+          float q[4];
+          load4(src + e * 4, q);
+          store4(dst + e * 4, q);
+        }
+      } else {
+        for (int e = li; e < (w >> 2); e += L) {
+          const float* s = src + e * 4;
+          const float q[4] = {s[0], s[1], s[2], s[3]};
+          store4(dst + e * 4, q);
+        }
+      }
+    } else {
+      for (int e = li; e < w; e += L) dst[e] = src[e];
+    }
+  }
+}
+
 // One-GPU stand-in for the RCCL all-reduce kernels of an overlapped data-parallel backward (a measurement aid,
 // tools/overlap_sim.py): nblk blocks that each take a whole CU (the launch asks for the CU's full LDS) and idle on the
 // real-time clock (100 MHz) for `ticks`, as an RCCL channel block holds its CU for a bucket's transfer time.
@@ -1139,6 +1200,34 @@ int cesm_window_gather_mv(const float* cond, const float* tgt, const int64_t* ti
   else
     window_gather_mv_kernel<false><<<grid, 256, 0, stream>>>(cond, tgt, times, meta, cwin, x0, sel, R, K, V, Vc, T, M,
                                                              H, W, h, w, L);
+  return cesm_launch_status();
+}
+
+int cesm_window_gather_mc(const float* cond, const float* tgt, const int64_t* times, const int64_t* meta, float* cwin,
+                          float* x0, int nitems, int K, int V, int Cc, int Vc, int csel0, int csel1, int csel2,
+                          int csel3, int T, int M, int H, int W, int h, int w, hipStream_t stream) {
+  if (Cc == V)
+    return cesm_window_gather_mv(cond, tgt, times, meta, cwin, x0, nitems, K, V, Vc, csel0, csel1, csel2, csel3, T, M,
+                                 H, W, h, w, stream);
+  if (!cond || !tgt || !times || !meta || !cwin || !x0) return CESM_EINVAL;
+  if (nitems < 1 || T < 1 || M < 1 || Vc < 1 || h < 1 || w < 1) return CESM_EINVAL;
+  if (V < 1 || V > 4 || Cc < 1 || Cc > 4 || K < 1 || h > H || w > W) return CESM_EUNSUPPORTED;
+  const int cs[4] = {csel0, csel1, csel2, csel3};
+  for (int c = 0; c < Cc; ++c)
+    if (cs[c] < 0 || cs[c] >= Vc) return CESM_EUNSUPPORTED;
+  const bool vec = w % 4 == 0 && (((uintptr_t)cwin | (uintptr_t)x0) & 15) == 0;
+  const int units = vec ? w / 4 : w;
+  const int passes = (int)cdiv(units, 256);
+  const int L = (int)cdiv(units, passes);
+  const int64_t R = (int64_t)nitems * (Cc * K + V) * h;
+  const unsigned grid = (unsigned)std::min<int64_t>(cdiv(R, 2 * (256 / L)), 2048);
+  const GatherSel sel = {csel0, csel1, csel2, csel3};
+  if (vec)
+    window_gather_mc_kernel<true><<<grid, 256, 0, stream>>>(cond, tgt, times, meta, cwin, x0, sel, R, K, V, Cc, Vc, T,
+                                                            M, H, W, h, w, L);
+  else
+    window_gather_mc_kernel<false><<<grid, 256, 0, stream>>>(cond, tgt, times, meta, cwin, x0, sel, R, K, V, Cc, Vc, T,
+                                                             M, H, W, h, w, L);
   return cesm_launch_status();
 }
 

@@ -584,4 +584,20 @@ int cesm_head_bwd_mv(int dtype, const float* dout, const void* x, const float* w
   return mv_head_bwd_launch(dtype, dout, x, w, dx, dw, db, part, nblk, B, V, F, HW, C, accumulate, stream);
 }
 
+// stem for V target variables and Cc conditioning maps (multivar.h; Cc == V runs the *_mv entry points above)
+int cesm_stem_fwd_mc(int dtype, const float* xt, const float* cond, const float* w, const float* bias, void* y, int B,
+                     int V, int Cc, int F, int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream) {
+  return mc_stem_fwd_launch(dtype, xt, cond, w, bias, y, B, V, Cc, F, Fx, Fc, H, W, Co, KS, stream);
+}
+int cesm_stem_wgrad_mc(int dtype, const float* xt, const float* cond, const void* dy, float* dw, float* part, int nblk,
+                       int B, int V, int Cc, int F, int Fx, int Fc, int H, int W, int Co, int KS, int accumulate,
+                       hipStream_t stream) {
+  return mc_stem_wgrad_launch(dtype, xt, cond, dy, dw, part, nblk, B, V, Cc, F, Fx, Fc, H, W, Co, KS, accumulate,
+                              stream);
+}
+int cesm_stem_dgrad_mc(int dtype, const void* dy, const float* w, float* dxt, float* dcond, int B, int V, int Cc, int F,
+                       int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream) {
+  return mc_stem_dgrad_launch(dtype, dy, w, dxt, dcond, B, V, Cc, F, Fx, Fc, H, W, Co, KS, stream);
+}
+
 }  // extern "C"

@@ -17,7 +17,9 @@ Multi-variable fields (T, M, C, H, W) and the random sample modes go through the
 host draws explicit frame indices per item (`WindowSampler.draw`) and `cesm_window_gather_mv` (or its numpy
 twin `host_gather_mv`) assembles `cond [B,V,K,h,w]`, `x0 [B,V,h,w]`.  `load_fields` loads and z-scores
 per variable and returns the statistics (`norm`) that `denormalize` and the checkpoint carry;
-`loader_from_config` builds either loader from a config's `dataset` / `train` sections.
+`loader_from_config` builds either loader from a config's `dataset` / `train` sections.  With `cond_channels=Cc` (a
+model built with `UNet(cond_channels=Cc)`) the loaders take Cc `cond_select` indices into the forcing variables and
+assemble `cond [B,Cc,K,h,w]` (`cesm_window_gather_mc` where Cc differs from V).
 """
 from __future__ import annotations
 
@@ -261,19 +263,42 @@ def host_gather(cond, tgt, items, K, h, w, center, out_c, out_x):
 
 
 def host_gather_mv(cond, tgt, times, meta, csel, h, w, out_c, out_x):
-    """numpy twin of cesm_window_gather_mv for the pinned path: out_c [n, V, K, h, w], out_x [n, V, h, w] (numpy views
-    of pinned buffers) from cond (T, M, Vc, H, W), tgt (T, M, V, H, W), times [n, K], meta [n, 4] = (member, anchor,
-    i, j) and the V forcing-plane indices csel."""
+    """numpy twin of cesm_window_gather_mv / cesm_window_gather_mc for the pinned path: out_c [n, Cc, K, h, w], out_x
+    [n, V, h, w] (numpy views of pinned buffers) from cond (T, M, Vc, H, W), tgt (T, M, V, H, W), times [n, K], meta
+    [n, 4] = (member, anchor, i, j) and the Cc forcing-plane indices csel (Cc = len(csel): V without cond_channels)."""
     csel = np.asarray(csel, dtype=np.int64)
+    if out_c.shape[1] != len(csel) or out_x.shape[1] != tgt.shape[2]:
+        raise ValueError(f"host_gather_mv: out_c has {out_c.shape[1]} planes for {len(csel)} cond_select indices, "
+                         f"out_x {out_x.shape[1]} for {tgt.shape[2]} target variables")
     for n, (tt, (m, anchor, i, j)) in enumerate(zip(times, meta)):
         for v, c in enumerate(csel):
             out_c[n, v] = cond[tt, m, c, i:i + h, j:j + w]
         out_x[n] = tgt[anchor, m, :, i:i + h, j:j + w]
 
 
-def resolve_cond_select(cond_select, Vc, V):
+MAX_COND = K.STEM_MAX_COND
+
+
+def resolve_cond_select(cond_select, Vc, V, cond_channels=None):
     """The V forcing-plane indices that feed the stem's V cond channels: identity when Vc == V, all zeros when there is
-    one forcing, anything else has to be given."""
+    one forcing, anything else has to be given.  cond_channels = Cc (a model built with UNet(cond_channels=Cc)): Cc
+    indices into the Vc forcing variables instead, identity when Vc == Cc, else they have to be given."""
+    if cond_channels is not None:
+        Cc = cond_channels
+        if isinstance(Cc, bool) or not isinstance(Cc, int) or not 1 <= Cc <= MAX_COND:
+            raise ValueError(f"cond_channels must be None or 1 … {MAX_COND}, got {Cc!r}")
+        if cond_select is None:
+            if Vc != Cc:
+                raise ValueError(f"cond has {Vc} variables and the model takes {Cc} conditioning maps: give "
+                                 f"cond_select= ({Cc} indices into the {Vc} cond variables)")
+            cond_select = range(Cc)
+        sel = [int(c) for c in cond_select]
+        if len(sel) != Cc:
+            raise ValueError(f"cond_select needs one index per conditioning map ({Cc}), got {sel}")
+        for c in sel:
+            if not 0 <= c < Vc:
+                raise ValueError(f"cond_select = {c} outside [0, {Vc - 1}]")
+        return sel
     if cond_select is None:
         if Vc == V:
             cond_select = range(V)
@@ -330,7 +355,9 @@ def shard_indices(n, batch_size, rank=0, world=1, shuffle=True, seed=0, epoch=0,
 
 
 class DeviceWindowLoader:
-    """HBM-resident fields + device gather kernel; iterate -> (cond [B,V,K,h,w], x0 [B,V,h,w]).
+    """HBM-resident fields + device gather kernel; iterate -> (cond [B,V,K,h,w], x0 [B,V,h,w]); with cond_channels=Cc
+    (a model built with UNet(cond_channels=Cc)) cond is [B,Cc,K,h,w] from Cc cond_select indices, through
+    cesm_window_gather_mc where Cc != V.
     (T, M, H, W) fields, or (T, M, 1, H, W), in consecutive mode: V = 1 through cesm_window_gather, as ever.
     (T, M, C, H, W) fields with more than one variable, or a random sample mode: cesm_window_gather_mv; cond_select
     names the forcing plane of each of the V cond channels (resolve_cond_select).
@@ -338,13 +365,17 @@ class DeviceWindowLoader:
 
     def __init__(self, cond, tgt, K, batch_size, device, center=True, crop_hw=None, crop_mode="random",
                  time_reverse_p=0.5, shuffle=True, seed=0, rank=0, world=1, *, cond_select=None,
-                 sample_mode="consecutive", window_radius=5, keep_chronology=True, causal=False, allow_replace=False):
+                 sample_mode="consecutive", window_radius=5, keep_chronology=True, causal=False, allow_replace=False,
+                 cond_channels=None):
         cond, tgt, single = _fields_5d(cond, tgt)
-        self.legacy = single and sample_mode == "consecutive"
+        self.legacy = single and sample_mode == "consecutive" and cond_channels is None
         if single and not self.legacy:
             cond, tgt = cond[:, :, None], tgt[:, :, None]
         T, M, H, W = cond.shape[0], cond.shape[1], cond.shape[-2], cond.shape[-1]
-        self.csel = None if self.legacy else resolve_cond_select(cond_select, cond.shape[2], tgt.shape[2])
+        self.csel = None if self.legacy else resolve_cond_select(cond_select, cond.shape[2], tgt.shape[2],
+                                                                 cond_channels)
+        # cond_channels maps that are not one per target variable: the gather with the plane counts separated
+        self.split = not self.legacy and len(self.csel) != tgt.shape[2]
         self.sampler = WindowSampler(T, M, H, W, K, center, crop_hw, crop_mode, time_reverse_p, sample_mode,
                                      window_radius=window_radius, keep_chronology=keep_chronology, causal=causal,
                                      allow_replace=allow_replace)
@@ -367,8 +398,8 @@ class DeviceWindowLoader:
         if not self.legacy:
             times, meta = self.sampler.draw(indices)
             self.last_row0 = torch.from_numpy(np.ascontiguousarray(meta[:, 2]))
-            return K.window_gather_mv(self.cond, self.tgt, torch.from_numpy(times), torch.from_numpy(meta), self.csel,
-                                      h, w)
+            gather = K.window_gather_mc if self.split else K.window_gather_mv
+            return gather(self.cond, self.tgt, torch.from_numpy(times), torch.from_numpy(meta), self.csel, h, w)
         it = self.sampler.items(indices)
         self.last_row0 = row0_of(it)
         n = it.shape[0]
@@ -391,15 +422,17 @@ class PinnedWindowLoader:
 
     def __init__(self, cond, tgt, K, batch_size, device, center=True, crop_hw=None, crop_mode="random",
                  time_reverse_p=0.5, shuffle=True, seed=0, rank=0, world=1, *, cond_select=None,
-                 sample_mode="consecutive", window_radius=5, keep_chronology=True, causal=False, allow_replace=False):
+                 sample_mode="consecutive", window_radius=5, keep_chronology=True, causal=False, allow_replace=False,
+                 cond_channels=None):
         cond, tgt, single = _fields_5d(cond, tgt)
-        self.legacy = single and sample_mode == "consecutive"
+        self.legacy = single and sample_mode == "consecutive" and cond_channels is None
         if single and not self.legacy:
             cond, tgt = cond[:, :, None], tgt[:, :, None]
         self.cond, self.tgt = cond, tgt
         T, M, H, W = cond.shape[0], cond.shape[1], cond.shape[-2], cond.shape[-1]
         V = 1 if self.legacy else tgt.shape[2]
-        self.csel = None if self.legacy else resolve_cond_select(cond_select, cond.shape[2], V)
+        self.csel = None if self.legacy else resolve_cond_select(cond_select, cond.shape[2], V, cond_channels)
+        Cc = V if self.legacy else len(self.csel)
         self.sampler = WindowSampler(T, M, H, W, K, center, crop_hw, crop_mode, time_reverse_p, sample_mode,
                                      window_radius=window_radius, keep_chronology=keep_chronology, causal=causal,
                                      allow_replace=allow_replace)
@@ -408,9 +441,9 @@ class PinnedWindowLoader:
         self.epoch = 0
         h, w = self.sampler.hw
         self.stream = torch.cuda.Stream(device=device)
-        self.host = [(torch.empty((batch_size, V, K, h, w)).pin_memory(),
+        self.host = [(torch.empty((batch_size, Cc, K, h, w)).pin_memory(),
                       torch.empty((batch_size, V, h, w)).pin_memory()) for _ in range(2)]
-        self.dev = [(torch.empty((batch_size, V, K, h, w), device=device),
+        self.dev = [(torch.empty((batch_size, Cc, K, h, w), device=device),
                      torch.empty((batch_size, V, h, w), device=device)) for _ in range(2)]
         self.done = [None, None]
         self.last_row0 = torch.zeros(0, dtype=torch.int64)
@@ -464,16 +497,22 @@ class PinnedWindowLoader:
             yield dc[:n], dx[:n]
 
 
-def loader_from_config(cfg, cond, tgt, device, kind="device", cond_select=None, shuffle=True, rank=0, world=1):
+def loader_from_config(cfg, cond, tgt, device, kind="device", cond_select=None, shuffle=True, rank=0, world=1,
+                       cond_channels=None):
     """The loader of a config (config/baseline, config/more_blocks): window and sampling options from cfg["dataset"]
     (K, center, crop_hw, crop_mode, time_reverse_p, sample_mode and, where present, window_radius, keep_chronology,
     causal, allow_replace), batch_size and seed from cfg["train"].  kind: "device" (DeviceWindowLoader) or "pinned"
-    (PinnedWindowLoader); cond / tgt as those take them, e.g. from load_fields."""
+    (PinnedWindowLoader); cond / tgt as those take them, e.g. from load_fields.  cond_channels: None reads
+    cfg["unet"]["cond_channels"] where the config has one (the model's), else as the loaders take it."""
     kinds = {"device": DeviceWindowLoader, "pinned": PinnedWindowLoader}
     if kind not in kinds:
         raise ValueError(f"kind must be 'device' or 'pinned', got {kind!r}")
     ds, tr = cfg["dataset"], cfg.get("train", {})
     extra = {k: ds[k] for k in ("window_radius", "keep_chronology", "causal", "allow_replace") if k in ds}
+    if cond_channels is None:
+        cond_channels = cfg.get("unet", {}).get("cond_channels")
+    if cond_channels is not None:
+        extra["cond_channels"] = cond_channels
     return kinds[kind](cond, tgt, ds["K"], tr.get("batch_size", 1), device, center=ds.get("center", True),
                        crop_hw=tuple(ds["crop_hw"]) if ds.get("crop_hw") else None,
                        crop_mode=ds.get("crop_mode", "random"), time_reverse_p=ds.get("time_reverse_p", 0.5),

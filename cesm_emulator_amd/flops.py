@@ -77,8 +77,8 @@ def unet_forward_macs(net, F, H, W):
 
 
 def stem_head_macs(net, F, H, W):
-    """(stem, head) per-sample MACs: the two terms that depend on the number of target variables V (the stem has 2V
-    input channels, the head V output channels); both are part of unet_forward_macs."""
+    """(stem, head) per-sample MACs: the two terms that depend on the number of target variables V (the stem has V +
+    Cc input channels -- 2V without cond_channels --, the head V output channels); both are part of unet_forward_macs."""
     ws, wh = net.input_conv.weight, net.out_conv[1].weight
     return F * H * W * ws.shape[0] * ws.shape[1] * ws.shape[-1] * ws.shape[-2], F * H * W * wh.shape[0] * wh.shape[1]
 

@@ -315,6 +315,70 @@ def stem_dgrad(dy, w, B, F, Fx, Fc, want_xt=True, want_cond=True):
     return dxt, dcond
 
 
+STEM_MAX_COND = 4  # conditioning maps of the stem (cesm_stem_*_mc): 1 .. 4, like the target variables
+
+
+def _stem_io_mc(xt, cond, cin, F):
+    """(B, V, Cc, Fx, Fc, H, W) of the multi-forcing stem's inputs: xt [B, V, Fx, H, W], cond [B, Cc, Fc, H, W] fp32,
+    V + Cc = the weight's input channels cin (V and Cc are read from the inputs, always 5-D here)"""
+    if xt.ndim != 5 or cond.ndim != 5:
+        raise ValueError(f"stem inputs must be [B, V, F, H, W] and [B, Cc, F, H, W], got {tuple(xt.shape)} and "
+                         f"{tuple(cond.shape)}")
+    B, V, Fx, H, W = xt.shape
+    Cc, Fc = cond.shape[1], cond.shape[2]
+    if V + Cc != cin:
+        raise RuntimeError(f"shape mismatch: stem weight with {cin} input channels, x_t has {V} and cond {Cc}")
+    _chk(xt, (B, V, Fx, H, W), torch.float32)
+    _chk(cond, (B, Cc, Fc, H, W), torch.float32)
+    if Fx not in (1, F) or Fc not in (1, F):
+        raise ValueError(f"stem: x_t has {Fx} frames and cond {Fc}; each must be 1 or F = {F}")
+    return B, V, Cc, Fx, Fc, H, W
+
+
+def stem_fwd_mc(xt, cond, w, b, F, dtype):
+    """stem Conv3d(V + Cc -> Co, (1,KS,KS)) on cat([x_t, cond]) with Cc conditioning maps (cesm_stem_fwd_mc): xt [B, V,
+    Fx, H, W], cond [B, Cc, Fc, H, W], w [Co, V + Cc, 1, KS, KS]; 1 <= V, Cc <= 4.  Cc == V runs what stem_fwd runs."""
+    Co, cin, _, KS, _ = w.shape
+    B, V, Cc, Fx, Fc, H, W = _stem_io_mc(xt, cond, cin, F)
+    _chk(w, (Co, cin, 1, KS, KS), torch.float32)
+    _chk(b, (Co,), torch.float32)
+    y = empty((B * F, H, W, Co), dtype, xt.device)
+    _mv_call("cesm_stem_fwd_mc", f"V={V} Cc={Cc} KS={KS} Co={Co} F={F} Fx={Fx} Fc={Fc}", _DT[dtype], P(xt), P(cond),
+             P(w), P(b), P(y), B, V, Cc, F, Fx, Fc, H, W, Co, KS, S())
+    return y
+
+
+def stem_wgrad_mc(xt, cond, dy, dw, F, accumulate=True):
+    """weight gradient of stem_fwd_mc: dw [Co, V + Cc, 1, KS, KS] fp32 (+)= ..."""
+    Co, cin, _, KS, _ = dw.shape
+    B, V, Cc, Fx, Fc, H, W = _stem_io_mc(xt, cond, cin, F)
+    _chk(dy, (B * F, H, W, Co))
+    _chk(dw, (Co, cin, 1, KS, KS), torch.float32)
+    nblk = 512
+    part = empty((nblk, Co * cin * KS * KS), torch.float32, xt.device)
+    _mv_call("cesm_stem_wgrad_mc", f"V={V} Cc={Cc} KS={KS} Co={Co} F={F} Fx={Fx} Fc={Fc}", dtcode(dy), P(xt), P(cond),
+             P(dy), P(dw), P(part), nblk, B, V, Cc, F, Fx, Fc, H, W, Co, KS, int(accumulate), S())
+
+
+def stem_dgrad_mc(dy, w, B, V, F, Fx, Fc, want_xt=True, want_cond=True):
+    """data gradient of stem_fwd_mc: w [Co, V + Cc, 1, KS, KS] and V give Cc.  Returns (dxt [B, V, Fx, H, W], dcond [B,
+    Cc, Fc, H, W]) fp32, None where not wanted; a frame-broadcast input gets the sum over the F frames."""
+    Nb, H, W, Co = dy.shape
+    KS = w.shape[-1]
+    cin = w.shape[1]
+    V = int(V)
+    Cc = cin - V
+    if V < 1 or Cc < 1:
+        raise ValueError(f"stem weight with {cin} input channels and V = {V}: no conditioning maps left")
+    _chk(dy, (B * F, H, W, Co))
+    _chk(w, (Co, cin, 1, KS, KS), torch.float32)
+    dxt = empty((B, V, Fx, H, W), torch.float32, dy.device) if want_xt else None
+    dcond = empty((B, Cc, Fc, H, W), torch.float32, dy.device) if want_cond else None
+    _mv_call("cesm_stem_dgrad_mc", f"V={V} Cc={Cc} KS={KS} Co={Co} F={F} Fx={Fx} Fc={Fc}", dtcode(dy), P(dy), P(w),
+             P(dxt), P(dcond), B, V, Cc, F, Fx, Fc, H, W, Co, KS, S())
+    return dxt, dcond
+
+
 def _head_v(w, C):
     if w.numel() == 0 or w.numel() % C:
         raise ValueError(f"head weight of shape {tuple(w.shape)} on {C} channels: expected [V, {C}]")
@@ -1235,11 +1299,11 @@ def window_gather(cond, tgt, items, K, h, w, center):
 GATHER_MAX_V = 4  # cesm_window_gather_mv takes csel by value
 
 
-def _gather_range(name, a, lo, hi):
+def _gather_range(name, a, lo, hi, fn="window_gather_mv"):
     """ValueError naming the field and the first value of the CPU int64 tensor a outside [lo, hi]"""
     bad = (a < lo) | (a > hi)
     if bool(bad.any()):
-        raise ValueError(f"window_gather_mv: {name} = {int(a[bad][0])} outside [{lo}, {hi}]")
+        raise ValueError(f"{fn}: {name} = {int(a[bad][0])} outside [{lo}, {hi}]")
 
 
 def window_gather_mv(cond, tgt, times, meta, csel, h, w, out=None):
@@ -1251,6 +1315,18 @@ def window_gather_mv(cond, tgt, times, meta, csel, h, w, out=None):
     CPU times / meta (what the loaders draw) are range-checked here, before anything is launched, and reach the device
     through one pinned staging buffer with a non-blocking copy; device times / meta are passed as they are and not read
     back (the kernel clamps every index)."""
+    return _window_gather("window_gather_mv", cond, tgt, times, meta, csel, h, w, out, None)
+
+
+def window_gather_mc(cond, tgt, times, meta, csel, h, w, out=None):
+    """window_gather_mv with the cond plane count separated from V (cesm_window_gather_mc): csel holds Cc indices (1 ..
+    4) into the Vc forcing planes, whatever V is.  Returns cwin [n, Cc, K, h, w], x0 [n, V, h, w]; everything else is
+    window_gather_mv's."""
+    return _window_gather("window_gather_mc", cond, tgt, times, meta, csel, h, w, out, len(csel))
+
+
+def _window_gather(fn, cond, tgt, times, meta, csel, h, w, out, ncond):
+    """the two gathers: ncond None is window_gather_mv (len(csel) must be V), else the count of cond planes"""
     for name, t, nd in (("cond", cond, 5), ("tgt", tgt, 5), ("times", times, 2), ("meta", meta, 2)):
         if not torch.is_tensor(t) or t.ndim != nd:
             raise RuntimeError(f"shape mismatch: {name} must be {nd}-D, got "
@@ -1268,20 +1344,22 @@ def window_gather_mv(cond, tgt, times, meta, csel, h, w, out=None):
             raise RuntimeError(f"dtype mismatch: {name} is {t.dtype}, expected {dt}")
     h, w = int(h), int(w)
     csel = [int(c) for c in csel]
-    if not 1 <= V <= GATHER_MAX_V or len(csel) != V or K < 1 or n < 1 or min(T, M, Vc, h, w) < 1 or h > H or w > W:
-        raise ValueError(f"window_gather_mv: unsupported shape V={V} (1 .. {GATHER_MAX_V}) csel={csel} K={K} n={n} "
+    Cc = V if ncond is None else int(ncond)
+    if (not 1 <= V <= GATHER_MAX_V or not 1 <= Cc <= GATHER_MAX_V or len(csel) != Cc or K < 1 or n < 1 or
+            min(T, M, Vc, h, w) < 1 or h > H or w > W):
+        raise ValueError(f"{fn}: unsupported shape V={V} (1 .. {GATHER_MAX_V}) csel={csel} K={K} n={n} "
                          f"crop {h} x {w} of {H} x {W}")
     for c in csel:
         if not 0 <= c < Vc:
-            raise ValueError(f"window_gather_mv: csel = {c} outside [0, {Vc - 1}]")
+            raise ValueError(f"{fn}: csel = {c} outside [0, {Vc - 1}]")
     if times.device != meta.device:
         raise RuntimeError(f"tensors on different devices: {times.device} and {meta.device}")
     if not times.is_cuda:
-        _gather_range("times", times, 0, T - 1)
-        _gather_range("member (meta[:, 0])", meta[:, 0], 0, M - 1)
-        _gather_range("anchor (meta[:, 1])", meta[:, 1], 0, T - 1)
-        _gather_range("i (meta[:, 2])", meta[:, 2], 0, H - h)
-        _gather_range("j (meta[:, 3])", meta[:, 3], 0, W - w)
+        _gather_range("times", times, 0, T - 1, fn)
+        _gather_range("member (meta[:, 0])", meta[:, 0], 0, M - 1, fn)
+        _gather_range("anchor (meta[:, 1])", meta[:, 1], 0, T - 1, fn)
+        _gather_range("i (meta[:, 2])", meta[:, 2], 0, H - h, fn)
+        _gather_range("j (meta[:, 3])", meta[:, 3], 0, W - w, fn)
     _chk(cond)
     _chk(tgt)
     if tgt.device != cond.device:
@@ -1299,17 +1377,21 @@ def window_gather_mv(cond, tgt, times, meta, csel, h, w, out=None):
         both = stage.to(cond.device, non_blocking=True)
         times, meta = both[:n * K].view(n, K), both[n * K:].view(n, 4)
     if out is None:
-        cwin = empty((n, V, K, h, w), torch.float32, cond.device)
+        cwin = empty((n, Cc, K, h, w), torch.float32, cond.device)
         x0 = empty((n, V, h, w), torch.float32, cond.device)
     else:
         cwin, x0 = out
-        _chk(cwin, (n, V, K, h, w), torch.float32)
+        _chk(cwin, (n, Cc, K, h, w), torch.float32)
         _chk(x0, (n, V, h, w), torch.float32)
         if cwin.device != cond.device or x0.device != cond.device:
             raise RuntimeError(f"tensors on different devices: {cwin.device}, {x0.device} and {cond.device}")
-    cs = csel + [0] * (GATHER_MAX_V - V)
-    _mv_call("cesm_window_gather_mv", f"V={V} Vc={Vc} csel={csel} K={K} crop {h} x {w} of {H} x {W}", P(cond), P(tgt),
-             P(times), P(meta), P(cwin), P(x0), n, K, V, Vc, *cs, T, M, H, W, h, w, S())
+    cs = csel + [0] * (GATHER_MAX_V - Cc)
+    if ncond is None:
+        _mv_call("cesm_window_gather_mv", f"V={V} Vc={Vc} csel={csel} K={K} crop {h} x {w} of {H} x {W}", P(cond),
+                 P(tgt), P(times), P(meta), P(cwin), P(x0), n, K, V, Vc, *cs, T, M, H, W, h, w, S())
+    else:
+        _mv_call("cesm_window_gather_mc", f"V={V} Cc={Cc} Vc={Vc} csel={csel} K={K} crop {h} x {w} of {H} x {W}",
+                 P(cond), P(tgt), P(times), P(meta), P(cwin), P(x0), n, K, V, Cc, Vc, *cs, T, M, H, W, h, w, S())
     return cwin, x0
 
 

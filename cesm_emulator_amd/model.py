@@ -28,7 +28,7 @@ class UNet(nn.Module):
                  attn_heads: int = 8, attn_dim_head: int = 32, use_sparse_linear_attn: bool = True,
                  use_mid_attn: bool = False, init_kernel_size: int = 7, use_checkpoint: bool = False,
                  use_temp_attn: bool = True, day_cond: bool = False, year_cond: bool = False,
-                 cond_map: bool = True):
+                 cond_map: bool = True, cond_channels=None):
         super().__init__()
         # what an identically shaped second instance is built from (ema.EMA's ema_model)
         self.ctor_kwargs = dict(in_channels=in_channels, out_channels=out_channels, base_ch=base_ch,
@@ -37,13 +37,13 @@ class UNet(nn.Module):
                                 use_sparse_linear_attn=use_sparse_linear_attn, use_mid_attn=use_mid_attn,
                                 init_kernel_size=init_kernel_size, use_checkpoint=use_checkpoint,
                                 use_temp_attn=use_temp_attn, day_cond=day_cond, year_cond=year_cond,
-                                cond_map=cond_map)
+                                cond_map=cond_map, cond_channels=cond_channels)
         self.net = UNetModel3D(n_vars=out_channels, model_dim=base_ch, dim_mults=tuple(ch_mults),
                                attn_heads=attn_heads, attn_dim_head=attn_dim_head,
                                use_sparse_linear_attn=use_sparse_linear_attn, use_mid_attn=use_mid_attn,
                                init_kernel_size=init_kernel_size, resnet_groups=groups,
                                use_checkpoint=use_checkpoint, use_temp_attn=use_temp_attn, day_cond=day_cond,
-                               year_cond=year_cond, cond_map=cond_map)
+                               year_cond=year_cond, cond_map=cond_map, cond_channels=cond_channels)
 
     @property
     def compute_dtype(self):
@@ -70,10 +70,14 @@ class UNet(nn.Module):
         Fx, Fc = x_t.shape[2], cond.shape[2]
         if Fx != Fc and not (Fx == 1 or Fc == 1):
             raise ValueError(f"Frame mismatch: x_t F={Fx}, cond F={Fc}")
-        V = self.net.n_vars
-        if x_t.shape[1] != V or cond.shape[1] != V:
-            raise ValueError(f"model with {V} target variable(s): x_t has {x_t.shape[1]} channels and cond "
-                             f"{cond.shape[1]}, both need {V}")
+        V, Cc = self.net.n_vars, self.net.n_cond
+        if Cc == V:
+            if x_t.shape[1] != V or cond.shape[1] != V:
+                raise ValueError(f"model with {V} target variable(s): x_t has {x_t.shape[1]} channels and cond "
+                                 f"{cond.shape[1]}, both need {V}")
+        elif x_t.shape[1] != V or cond.shape[1] != Cc:
+            raise ValueError(f"model with {V} target variable(s) and {Cc} conditioning map(s) (cond_channels): x_t has "
+                             f"{x_t.shape[1]} channels and cond {cond.shape[1]}; they need {V} and {Cc}")
         if not x_t.is_cuda:
             raise RuntimeError("cesm_emulator_amd.UNet runs on the GPU only (move model and inputs to 'cuda')")
         if not torch.is_tensor(t):
@@ -587,17 +591,23 @@ class Diffusion(nn.Module):
         return self._sample_ensemble(cond, members, device, steps, ddim_eta, member_batch, x_T, noise_seq, use_graph,
                                      False, solver=solver, spacing=spacing, guidance_scale=guidance_scale)
 
+    def _n_vars(self, cond):
+        """target variables of a sample: the network's n_vars (a model without one, e.g. a test double: cond's)"""
+        net = getattr(self.model, "net", None)
+        return int(getattr(net, "n_vars", cond.shape[1]))
+
     def _sample_ensemble(self, cond, members, device, steps, ddim_eta, member_batch, x_T, noise_seq, use_graph, paired,
                          solver="ddim", spacing=None, guidance_scale=None):
         """sample_ensemble(); paired: cond is two halves [cond, cond2] whose jobs b M + m get the same x_T and step
         noise (one chunk only: counterfactual_delta)"""
         if cond.ndim not in (4, 5):
-            raise ValueError(f"cond must be [B, V, H, W] or [B, V, Fc, H, W], got {tuple(cond.shape)}")
+            raise ValueError(f"cond must be [B, Cc, H, W] or [B, Cc, Fc, H, W], got {tuple(cond.shape)}")
         M = int(members)
         if M < 1:
             raise ValueError(f"members must be >= 1, got {members}")
         device = cond.device if device is None else torch.device(device)
-        B, V, H, W = cond.shape[0], cond.shape[1], cond.shape[-2], cond.shape[-1]
+        # V is the network's: cond carries cond_channels maps, which need not be V
+        B, V, H, W = cond.shape[0], self._n_vars(cond), cond.shape[-2], cond.shape[-1]
         jobs = B * M
         mb = jobs if member_batch is None else int(member_batch)
         if mb < 1:

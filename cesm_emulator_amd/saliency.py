@@ -17,7 +17,8 @@ from .video_net import input_grads_only
 
 def input_grads(diffusion, x0, cond, t=None, noise=None, keep=None):
     """(loss, d loss / d x_t, d loss / d cond) of the eps-prediction MSE at x_t = q_sample(x0, t, noise).
-    x0 [B,V,H,W]; cond [B,V,H,W] (F = 1) or a window [B,V,F,H,W]; t defaults to T // 2 for every sample.  The
+    x0 [B,V,H,W]; cond [B,Cc,H,W] (F = 1) or a window [B,Cc,F,H,W] (Cc = the model's cond_channels, V by default); t
+    defaults to T // 2 for every sample.  The
     gradients have x_t's (= x0's) and cond's shapes and are fp32; loss is detached.  keep (bool [B], the condition
     dropout of Diffusion.loss): the samples with keep False see the null condition, and their d cond is exactly zero;
     nothing is drawn here, whatever the diffusion's p_uncond."""
@@ -61,7 +62,8 @@ def counterfactual_delta(diffusion, cond, scale_mask=None, scale=1.1, steps=None
     if n_samples < 1:
         raise ValueError(f"n_samples must be >= 1, got {n_samples}")
     cond2 = cond * scale if scale_mask is None else cond * (1.0 + (scale - 1.0) * scale_mask)
-    B, V, H, W = cond.shape[0], cond.shape[1], cond.shape[-2], cond.shape[-1]  # V target variables, as cond has
+    # V target variables: the network's (cond carries cond_channels maps, which need not be V)
+    B, V, H, W = cond.shape[0], diffusion._n_vars(cond), cond.shape[-2], cond.shape[-1]
     kw = dict(solver=solver, spacing=spacing, guidance_scale=guidance_scale)
     if n_samples > 1:
         if paired:

@@ -27,7 +27,8 @@ def build_model_from_config(cfg_unet):
                 base_ch=cfg_unet.get("base_ch", 64), ch_mults=tuple(cfg_unet.get("ch_mults", (1, 2, 4))),
                 num_res_blocks=cfg_unet.get("num_res_blocks", 2), time_dim=cfg_unet.get("time_dim", 256),
                 groups=cfg_unet.get("groups", 8), use_checkpoint=cfg_unet.get("use_checkpoint", True),
-                dropout=cfg_unet.get("dropout", 0.0), use_temp_attn=cfg_unet.get("use_temp_attn", True))
+                dropout=cfg_unet.get("dropout", 0.0), use_temp_attn=cfg_unet.get("use_temp_attn", True),
+                cond_channels=cfg_unet.get("cond_channels"))
 
 
 def rank_generator(device, seed=2, rank=0):

@@ -134,6 +134,8 @@ _INPUTS_ONLY = [False]
 
 # target variables the stem and head kernels take (csrc/multivar.h: 2V input planes, V head outputs)
 MAX_VARS = 4
+# conditioning maps the stem kernels take (cesm_stem_*_mc: V + Cc input planes)
+MAX_COND = K.STEM_MAX_COND
 
 
 class input_grads_only:
@@ -755,7 +757,8 @@ def sla_bwd(rc, res_mod, st, dy):
 class UNetModel3D(nn.Module):
     def __init__(self, n_vars, model_dim, dim_mults=(1, 2, 4, 8), attn_heads=8, attn_dim_head=32,
                  use_sparse_linear_attn=True, use_mid_attn=False, init_kernel_size=7, resnet_groups=8,
-                 use_checkpoint=False, use_temp_attn=True, day_cond=False, year_cond=False, cond_map=True):
+                 use_checkpoint=False, use_temp_attn=True, day_cond=False, year_cond=False, cond_map=True,
+                 cond_channels=None):
         super().__init__()
         if not cond_map or day_cond or year_cond or use_mid_attn:
             raise NotImplementedError("only the configurations model.UNet builds are supported "
@@ -764,8 +767,16 @@ class UNetModel3D(nn.Module):
             raise NotImplementedError(f"n_vars must be 1 … {MAX_VARS} target variables (the stem and head kernels' "
                                       f"limit), got {n_vars}")
         self.n_vars = n_vars
+        # conditioning maps of the stem (multi-forcing conditioning): None = one per target variable, the reference's
+        if cond_channels is None:
+            cond_channels = n_vars
+        if isinstance(cond_channels, bool) or not isinstance(cond_channels, int) or \
+                not 1 <= cond_channels <= MAX_COND:
+            raise NotImplementedError(f"cond_channels must be None or 1 … {MAX_COND} conditioning maps (the stem "
+                                      f"kernels' limit), got {cond_channels!r}")
+        self.n_cond = cond_channels
         self.compute_dtype = torch.bfloat16
-        in_ch = 2 * n_vars
+        in_ch = n_vars + self.n_cond
         pad = init_kernel_size // 2
         self.input_conv = nn.Conv3d(in_ch, model_dim, (1, init_kernel_size, init_kernel_size),
                                     padding=(0, pad, pad))
@@ -870,7 +881,7 @@ class UNetModel3D(nn.Module):
 
     # ---------------------------------------------------------------- executor
     def run_forward(self, x_t, cond, t, save):
-        """x_t [B,V,Fx,H,W], cond [B,V,Fc,H,W] fp32, t int64 [B]; returns [B,V,H,W] (frame F//2)."""
+        """x_t [B,V,Fx,H,W], cond [B,Cc,Fc,H,W] fp32 (Cc = n_cond), t int64 [B]; returns [B,V,H,W] (frame F//2)."""
         B, _, Fx, H, W = x_t.shape
         F = max(Fx, cond.shape[2])
         cdt = self.compute_dtype
@@ -880,7 +891,9 @@ class UNetModel3D(nn.Module):
         rc.rot = K.rope_table(self.mid_temporal_attn.fn.fn.fn.rotary_emb.freqs, F)
         tape = SimpleNamespace(rc=rc, x_t=x_t, cond=cond, downs=[], ups=[])
 
-        x = K.stem_fwd(x_t, cond, self.input_conv.weight, self.input_conv.bias, F, cdt)
+        # Cc == V is the stem as it always was; another cond plane count takes the multi-forcing entries
+        stem_fwd = K.stem_fwd if self.n_cond == self.n_vars else K.stem_fwd_mc
+        x = stem_fwd(x_t, cond, self.input_conv.weight, self.input_conv.bias, F, cdt)
         tape.stem_out = x
         x, tape.in_attn = temporal_fwd(rc, self.input_temp_op, x)
         r = x
@@ -998,15 +1011,20 @@ class UNetModel3D(nn.Module):
         dx = K.add(dx, dr)
         dx = temporal_bwd(rc, self.input_temp_op, tape.in_attn, dx)
         wi, bi = gbuf(self.input_conv.weight), gbuf(self.input_conv.bias)
+        mono = self.n_cond == self.n_vars  # the stem kernels of run_forward
         with rc.side(tape.x_t, tape.cond, dx):
             if wi is not None:
-                K.stem_wgrad(tape.x_t, tape.cond, dx, wi, rc.F)
+                (K.stem_wgrad if mono else K.stem_wgrad_mc)(tape.x_t, tape.cond, dx, wi, rc.F)
             if bi is not None:
                 K.colsum(dx, bi)
         dxt = dcond = None
         if want_xt or want_cond:  # input gradients: the stem's data gradient, on the main stream
-            dxt, dcond = K.stem_dgrad(dx, self.input_conv.weight, rc.B, rc.F, tape.x_t.shape[2], tape.cond.shape[2],
-                                      want_xt, want_cond)
+            if mono:
+                dxt, dcond = K.stem_dgrad(dx, self.input_conv.weight, rc.B, rc.F, tape.x_t.shape[2],
+                                          tape.cond.shape[2], want_xt, want_cond)
+            else:
+                dxt, dcond = K.stem_dgrad_mc(dx, self.input_conv.weight, rc.B, self.n_vars, rc.F, tape.x_t.shape[2],
+                                             tape.cond.shape[2], want_xt, want_cond)
             # kernels.stem_dgrad leaves the variable axis out at V = 1; the forward's inputs had it
             dxt = None if dxt is None else dxt.view(tape.x_t.shape)
             dcond = None if dcond is None else dcond.view(tape.cond.shape)

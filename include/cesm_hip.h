@@ -152,6 +152,20 @@ int cesm_head_fwd_mv(int dtype, const void* x, const float* w, const float* bias
                      int HW, int C, hipStream_t stream);
 int cesm_head_bwd_mv(int dtype, const float* dout, const void* x, const float* w, void* dx, float* dw, float* db,
                      float* part, int nblk, int B, int V, int F, int HW, int C, int accumulate, hipStream_t stream);
+/* The stem with the number of conditioning maps Cc separated from the number of target variables V (multi-forcing
+ * conditioning; csrc/multivar.h), 1 <= V <= 4 and 1 <= Cc <= 4: Conv3d(P -> Co), P = V + Cc, on cat([x_t, cond]).
+ * xt [B][V][Fx][H][W], cond [B][Cc][Fc][H][W], w / dw [Co][P][KS][KS] with input channels 0..V-1 = x_t and V..P-1 =
+ * cond, part nblk*Co*P*KS*KS floats, dxt shaped like xt and dcond like cond (each nullable).  Every other argument is
+ * that of the *_mv entry, and Cc == V IS the *_mv entry (same kernels, same grids; V = Cc = 1 the single-variable
+ * one).  CESM_EUNSUPPORTED for V or Cc outside 1..4 and for the stem shapes cesm_stem_dgrad refuses.  Deterministic.
+ * (Added entry points: the ABI version stays.) */
+int cesm_stem_fwd_mc(int dtype, const float* xt, const float* cond, const float* w, const float* bias, void* y, int B,
+                     int V, int Cc, int F, int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream);
+int cesm_stem_wgrad_mc(int dtype, const float* xt, const float* cond, const void* dy, float* dw, float* part, int nblk,
+                       int B, int V, int Cc, int F, int Fx, int Fc, int H, int W, int Co, int KS, int accumulate,
+                       hipStream_t stream);
+int cesm_stem_dgrad_mc(int dtype, const void* dy, const float* w, float* dxt, float* dcond, int B, int V, int Cc, int F,
+                       int Fx, int Fc, int H, int W, int Co, int KS, hipStream_t stream);
 
 /* ---- normalisation (csrc/norm.hip) -------------------------------------------------------
  * GroupNorm(G,C) eps, affine, then x*(scale+1)+shift, SiLU, + residual: video_net.py:216-227, :265. */
@@ -544,6 +558,16 @@ int cesm_window_gather(const float* cond, const float* tgt, const int64_t* items
 int cesm_window_gather_mv(const float* cond, const float* tgt, const int64_t* times, const int64_t* meta, float* cwin,
                           float* x0, int nitems, int K, int V, int Vc, int csel0, int csel1, int csel2, int csel3,
                           int T, int M, int H, int W, int h, int w, hipStream_t stream);
+/* cesm_window_gather_mv with the cond plane count Cc separated from V (multi-forcing conditioning), 1 <= V, Cc <= 4:
+ *   csel0 .. csel3: csel[c] in [0, Vc) names the forcing plane that feeds cond channel c < Cc (entries >= Cc ignored);
+ *   cwin[n][c][k][y][x] = cond[times[n][k]][m][csel[c]][i + y][j + x]     cwin [nitems][Cc][K][h][w]
+ *   x0[n][v][y][x]      = tgt[anchor][m][v][i + y][j + x]                 x0   [nitems][V][h][w]
+ * Work units are (n, plane in Cc K + V, y).  Clamping, 64-bit offsets, the vector / element paths and the return codes
+ * are those of cesm_window_gather_mv (CESM_EUNSUPPORTED also for Cc outside 1 .. 4).  (Added entry point: the ABI
+ * version stays.) */
+int cesm_window_gather_mc(const float* cond, const float* tgt, const int64_t* times, const int64_t* meta, float* cwin,
+                          float* x0, int nitems, int K, int V, int Cc, int Vc, int csel0, int csel1, int csel2,
+                          int csel3, int T, int M, int H, int W, int h, int w, hipStream_t stream);
 
 #ifdef __cplusplus
 }
